@@ -3,6 +3,26 @@ correspondence + IEKF + map maintenance + LM solve) on synthetic LiDAR-inertial
 sequences, MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--lidar 64line] [--config mid360]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it generates the W + K
+scans, warms up, times the K scans and prints the result line (the per-kernel
+figures in it come from the in-kernel clocks of the timed scans themselves).
+--full adds every other leg, each a run of its own: the per-stage pass, the
+host-input and sharded-path rates, the CPU baseline and the ATE against it,
+the 128-line target workloads and the multi-sequence legs (--no-cpu,
+--stage-scans, --target-steps, --no-h2d, --no-tile1, --multi and --multi-1m
+select among them and mean nothing without --full; the host-input,
+sharded-path and multi-sequence legs time min(K, 40) scans, so a long metric
+leg does not multiply into sixteen long sequences). --dump-outputs DIR writes
+what a caller of the timed path holds after the last timed scan as
+DIR/<name>.npy (float64): trajectory (vg_trajectory), path (vg_path), state
+(vg_get_state) and counters (the timed scans' vg_stats_log integer counters).
+The scans are a pure function of the arguments (synth.py's seeds), so two
+builds run with the same arguments can be compared array for array (measured:
+bit-identical from run to run). Compare like with like: legs that load scans
+past the timed ones (--full's per-stage pass and CPU sample) size the context
+by the largest scan loaded, which moves the poses at the 1e-14 m level.
 
 N > 1 is launched by torch.distributed.run: one process per GPU, each running an
 independent sequence (replica mode, "scaling": "weak" — the path has no
@@ -13,7 +33,7 @@ window is full, so every timed scan is a steady-state scan. Inputs are resident
 in HBM before timing starts (vg_step_dev); the host-input rate (vg_step, H2D
 copy inside) is reported beside it.
 
-Rank 0 at N = 1 also times the CPU restatement (oracle, test infrastructure) on
+With --full, rank 0 at N = 1 also times the CPU restatement (oracle, test infrastructure) on
 a bounded sample of the same sequence (5 worker threads as the reference, and
 1 thread): the cpu_baseline object, and the GPU trajectory's ATE against it.
 """
@@ -54,13 +74,19 @@ class _StdoutToStderr:
         os.close(self.saved)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--lidar", default="64line")
     ap.add_argument("--config", default="mid360")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the metric's (per-stage pass, host-input and sharded-path rates, "
+                         "CPU baseline and ATE, 128-line targets, multi-sequence legs); off: the metric leg alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed by its last timed scan as DIR/<name>.npy (float64): "
+                         "trajectory, path, state, counters")
     ap.add_argument("--cpu-warmup", type=int, default=20, help="oracle warm-up scans (BASELINE.md: 20)")
     ap.add_argument("--cpu-scans", type=int, default=200,
                     help="oracle sample: timed scans after its warm-up (BASELINE.md: >= 200)")
@@ -94,7 +120,12 @@ def parse():
     ap.add_argument("--multi-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--multi-scans", default="", help=argparse.SUPPRESS)
     ap.add_argument("--multi-max-points", type=int, default=0, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:  # the metric leg alone: every other leg is a run of its own
+        args.no_cpu = args.no_h2d = args.no_tile1 = True
+        args.stage_scans = args.target_steps = 0
+        args.multi = args.multi_1m = ""
+    return args
 
 
 T_START = time.perf_counter()
@@ -122,15 +153,20 @@ def _gen(job):
     return xyz, inten, b, e, seq.imu(k)
 
 
-def gen_scans(lidar, seq_id, general, n, workers):
+def gen_scans(lidar, seq_id, general, n, workers, meanwhile=None):
+    """meanwhile: host-only work of the caller's (an import) done while the pool generates."""
     jobs = [(lidar, seq_id, general["blind"], general["extrinsic_rota"], general["extrinsic_tran"], k)
             for k in range(n)]
     if workers <= 1 or n <= 2 or under_profiler():
         return [_gen(j) for j in jobs]
     with mproc.get_context("fork").Pool(min(workers, n)) as pool:
-        return pool.map(_gen, jobs, chunksize=1)
+        res = pool.map_async(_gen, jobs, chunksize=1)
+        if meanwhile is not None:
+            meanwhile()
+        return res.get()
 
 
+LEG_STEPS_MAX = 40  # --steps' default: what the host-input, sharded-path and multi-sequence legs time at most
 CAP = {}  # context capacities (--max-nodes / --max-fix / --hash-log2; 0 = the product's defaults)
 
 
@@ -153,6 +189,9 @@ def main():
     W = p["LocalBA"]["win_size"]
     warmup = max(args.warmup, W + 2)
     total = warmup + args.steps
+    # the legs beside the metric's (--full) time at most LEG_STEPS_MAX scans each, whatever --steps asks of the
+    # metric leg: sixteen sequences of --steps scans would take the run from minutes to hours
+    leg_steps = min(args.steps, LEG_STEPS_MAX)
     if args.multi_child:
         return multi_child(args, p, g, warmup, total)
     cpu_on = rank == 0 and world == 1 and not args.no_cpu
@@ -163,7 +202,8 @@ def main():
     seq_id = args.seq + (0 if tile else rank)
     beat("generating %d %s scans (workers %d%s)" % (n_need, args.lidar, workers,
                                                    ", in-process: profiler" if under_profiler() else ""))
-    host_scans = gen_scans(args.lidar, seq_id, g, n_need, workers)
+    # (torch's import, a few seconds of host work that touches no GPU, overlaps the pool's generation)
+    host_scans = gen_scans(args.lidar, seq_id, g, n_need, workers, meanwhile=lambda: __import__("torch"))
     tgt_scans = {}
     if world == 1 and args.target_steps > 0 and args.lidar != "128line":
         for cfg in ("mid360", "robosense"):
@@ -174,8 +214,8 @@ def main():
 
     multi, multi_1m, scans_1m = None, None, None
     if world == 1 and args.multi:
-        multi = multi_children(args, args.lidar, args.multi, warmup, args.steps, workers,
-                               first=host_scans[:total])
+        multi = multi_children(args, args.lidar, args.multi, warmup, leg_steps, workers,
+                               first=host_scans[:warmup + leg_steps])
     if world == 1 and args.multi_1m:
         keep = []  # sequence 0 of the leg, plus TARGET_STAGE scans: its single-context roofline (workload_roofline)
         multi_1m = multi_children(args, "1M", args.multi_1m, warmup, args.multi_1m_steps, workers, keep=keep)
@@ -258,6 +298,8 @@ def main():
     dt = time.perf_counter() - t0
     stats = ctx.stats_log()[nlog0:]  # completes the last scan's bookkeeping (outside the timed region)
     prof = ctx.profile_read()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, stats)
     value, dt = aggregate(dt, args.steps, world, dev)
     if tile:  # every rank worked on the same scans
         value /= world
@@ -406,11 +448,11 @@ def main():
     h2d = None
     if world == 1 and not args.no_h2d:
         beat("host-input leg")
-        h2d = leg("host_input", lambda: host_input_rate(p, seq, host_scans, imus, warmup, args.steps, dev))
+        h2d = leg("host_input", lambda: host_input_rate(p, seq, host_scans, imus, warmup, leg_steps, dev))
     tile1 = None
     if world == 1 and not args.no_tile1:
         beat("sharded-path leg on one GPU")
-        tile1 = leg("tile_path_1gpu", lambda: tile_path_rate(p, seq, scans, imus, warmup, args.steps, dev, value))
+        tile1 = leg("tile_path_1gpu", lambda: tile_path_rate(p, seq, scans, imus, warmup, leg_steps, dev, value))
     cpu, ate_cpu = None, None
     if cpu_on:
         beat("CPU baseline: %d + %d scans, 5 threads then 1" % (args.cpu_warmup, args.cpu_scans))
@@ -449,7 +491,7 @@ def main():
             "metric": METRIC, "value": round(value, 3), "unit": "scans/s", "n_gpus": world, "steps": args.steps,
             "warmup": warmup, "warmup_requested": args.warmup, "ms_per_step": round(dt * 1e3 / args.steps, 4),
             "higher_is_better": True, "scaling": "strong" if tile else "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full), "dumped_outputs": args.dump_outputs or None,
             "config": {"workload": "synthetic-%s@%s.yaml" % (args.lidar, args.config), "lidar": args.lidar,
                        "rays_per_scan": int(synth.LIDARS[args.lidar][0] * synth.LIDARS[args.lidar][1]),
                        "points_per_scan": npts, "downsampled_per_scan": int(np.mean([s["n_ds"] for s in stats])),
@@ -482,6 +524,20 @@ def main():
             sys.exit(3)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, ctx, stats):
+    """--dump-outputs: what a caller of the timed path holds once the last
+    timed scan has completed, one float64 .npy per array (a few hundred kB in
+    all): the pose of every scan so far (vg_trajectory), the published path
+    (vg_path), the filter state (vg_get_state) and the timed scans' counters
+    (vg_stats_log, one row per scan, fields in Stats order, arrays flattened)."""
+    os.makedirs(path, exist_ok=True)
+    rows = [np.hstack([np.ravel(v) for v in s.values()]) for s in stats]
+    out = {"trajectory": ctx.trajectory(), "path": ctx.path(), "state": ctx.state(),
+           "counters": np.array(rows).reshape(len(stats), -1)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def scan_roofline(stats, stage_stats, W, t_scan, pk_scans=None):

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B/C of three builds of the library on the same box: A = lib/, B = lib_alt/, C = lib_alt2/ (3 rounds)
 set -o pipefail
+AB_ARGS="--full ${AB_ARGS}"  # the sharded-path and multi-sequence legs beside the metric, unless AB_ARGS drops them
 mkdir -p gpurun_out
 for i in 1 2 3; do
   for v in A B C; do

@@ -1,6 +1,6 @@
 set -o pipefail
 mkdir -p gpurun_out
-A="--no-cpu --stage-scans 8 --target-steps 0 --no-h2d --no-tile1 --multi= --multi-1m="
+A="--full --no-cpu --stage-scans 8 --target-steps 0 --no-h2d --no-tile1 --multi= --multi-1m="
 for i in 1 2; do
 for K in 40 200; do
 timeout -k 10 200 python bench.py $A --steps $K > gpurun_out/st_${K}_$i.json 2>/dev/null || exit 1

@@ -104,6 +104,8 @@ class Scene:
         """Ray-cast from origin o ((3,) or per ray (n,3)) along unit dirs d (n,3). Returns ranges (n,) and
         surface id."""
         n = d.shape[0]
+        o = np.asarray(o, dtype=np.float64)
+        one = o.ndim == 1
         o2 = np.broadcast_to(o, d.shape)
         best = np.full(n, np.inf)
         sid = np.full(n, -1, dtype=np.int32)
@@ -114,14 +116,27 @@ class Scene:
                     ok = (t > 1e-6) & (t < best)
                     best = np.where(ok, t, best)
                     sid = np.where(ok, 2 * ax + k, sid)
+            # Every matrix-vector product keeps its (n,3) shape: a BLAS may round a row by where it
+            # lies in the matrix, so the bits of a scan stay those of the all-rays formulation
+            # (tests/test_synth_cast.py) only if each row keeps its place. The element-wise work is
+            # done only on the rays whose plane hit is the nearest so far; the other rows of q hold
+            # stale values, which nothing reads.
+            co = np.empty(d.shape)
+            q = np.zeros(d.shape)
             for j, (c, nrm, a, b, ha, hb) in enumerate(self.panels):
                 den = d @ nrm
-                t = ((c[None, :] - o2) @ nrm) / den
-                p = o2 + t[:, None] * d
-                q = p - c[None, :]
-                ok = (t > 1e-6) & (t < best) & (np.abs(q @ a) <= ha) & (np.abs(q @ b) <= hb)
-                best = np.where(ok, t, best)
-                sid = np.where(ok, 6 + j, sid)
+                if one:  # every row is c - o
+                    co[:, 0], co[:, 1], co[:, 2] = c - o
+                else:
+                    co[:] = c[None, :] - o2
+                t = (co @ nrm) / den
+                idx = np.flatnonzero((t > 1e-6) & (t < best))
+                ti = t[idx]
+                q[idx] = ((o if one else o2[idx]) + ti[:, None] * d[idx]) - c[None, :]
+                ok = (np.abs((q @ a)[idx]) <= ha) & (np.abs((q @ b)[idx]) <= hb)
+                hit = idx[ok]
+                best[hit] = ti[ok]
+                sid[hit] = 6 + j
         best[best > max_range] = np.inf
         return best, sid
 
