@@ -33,7 +33,7 @@ def main(nscan=40, lidar="64line"):
         ctx.step(xyz, it, b, e, seq.imu(k))
         if k == 11:
             L.vg_probe_read(buf, 64)  # clear the warm-up
-            L.vg_probe_read_map(buf, 64)
+            L.vg_probe_read_recut(buf, 64)
     L.vg_probe_read(buf, 64)
     calls = max(buf[63], 1)
     print("k_ba_solve real calls:", buf[63])
@@ -45,7 +45,7 @@ def main(nscan=40, lidar="64line"):
     print("  %-16s %8.2f us/call" % ("total", tot))
     for k, name in EXTRA.items():
         print("  %8.2f us/call %s" % (buf[k] * 0.01 / calls, name))
-    L.vg_probe_read_map(buf, 64)
+    L.vg_probe_read_recut(buf, 64)
     na = max(buf[62], 1)
     print("k_rc_apply calls:", buf[62])
     for k, name in {16: "sort subs+events", 17: "child alloc", 18: "keys", 19: "bitonic", 20: "push", 21: "finish"}.items():
@@ -69,8 +69,9 @@ def iekf(nscan=40, lidar="64line"):
         ctx.step(xyz, it, b, e, seq.imu(k))
         ctx.stats()
         if k == 11:
-            L.vg_probe_read_map(buf, 64)
-    L.vg_probe_read_map(buf, 64)
+            L.vg_probe_read_iekf(buf, 64)  # clear the warm-up
+            L.vg_probe_read_margi(buf, 64)
+    L.vg_probe_read_iekf(buf, 64)
     n, nf = max(buf[61], 1), max(buf[60], 1)
     print("iekf updates:", buf[61], "final:", buf[60])
     for k, name in {24: "reduce partials", 25: "K6 (6x6 solve)", 26: "G6/vec/sol", 27: "plus/conv"}.items():
@@ -81,6 +82,7 @@ def iekf(nscan=40, lidar="64line"):
     print("k_iekf block 0, thread 0:", buf[59], "launches")
     for k, name in {30: "point loop", 31: "block reduction"}.items():
         print("  %-16s %8.2f us/launch" % (name, buf[k] * 0.01 / ni))
+    L.vg_probe_read_margi(buf, 64)
     nb = max(buf[47], 1)
     print("k_margi_leaf: %d working blocks, leaves (max) %d" % (buf[47], buf[50]))
     print("  %-16s %8.2f us" % ("mean block span", buf[46] * 0.01 / nb))

@@ -34,9 +34,9 @@ def main(nscan=30):
         ctx.step(xyz, it, b, e, seq.imu(k))
         if k == 11:
             ctx.stats_log()
-            L.vg_probe_read_map(buf, 64)  # clear the warm-up
+            L.vg_probe_read_iekf(buf, 64)  # clear the warm-up
     ctx.stats_log()
-    L.vg_probe_read_map(buf, 64)
+    L.vg_probe_read_iekf(buf, 64)
     calls, fin, kcalls = max(buf[61], 1), max(buf[60], 1), max(buf[59], 1)
     print("k_iekf_update calls: %d (finishing %d); k_iekf calls: %d" % (buf[61], buf[60], buf[59]))
     for k, name in UPD.items():

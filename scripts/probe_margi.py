@@ -32,9 +32,9 @@ def main(nscan=30):
         ctx.step(xyz, it, b, e, seq.imu(k))
         if k == 11:
             ctx.stats_log()
-            L.vg_probe_read_map(buf, 64)  # clear the warm-up
+            L.vg_probe_read_margi(buf, 64)  # clear the warm-up
     ctx.stats_log()
-    L.vg_probe_read_map(buf, 64)
+    L.vg_probe_read_margi(buf, 64)
     nl = max(buf[56], 1)
     print("k_margi_leaf: %d live leaves (%d with a factor) over %d scans; longest leaf %.2f us; "
           "longest block %.2f us" % (buf[56], buf[58], nscan - 12, buf[57] / 100.0, buf[45] / 100.0))

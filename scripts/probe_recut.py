@@ -32,9 +32,9 @@ def main(nscan=40):
         ctx.step(xyz, it, b, e, seq.imu(k))
         if k == 11:
             ctx.stats_log()
-            L.vg_probe_read_map(buf, 64)  # clear the warm-up
+            L.vg_probe_read_recut(buf, 64)  # clear the warm-up
     ctx.stats_log()
-    L.vg_probe_read_map(buf, 64)
+    L.vg_probe_read_recut(buf, 64)
     for lev, pb in ((0, 0), (1, 8), (2, 32)):
         n = max(buf[pb], 1)
         print("level %d: %d calls, nsub %.1f, children %.1f, other nodes %.1f" %

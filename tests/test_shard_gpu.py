@@ -101,7 +101,7 @@ def test_two_shards_match_one(cfgname, lidar, nscan):
         # the match count is part of the all-reduced normal equations: global on every rank
         assert a["iekf_matches"] == b["iekf_matches"] == c["iekf_matches"], k
     # per-rank work: each rank's IEKF transforms and matches only the points of
-    # its tiles plus a 0.1 m band, not the whole scan (map.hip k_keep_*). The
+    # its tiles plus a 0.1 m band, not the whole scan (iekf.hip k_keep_*). The
     # synthetic box's floor lies on the z = 0 tile face, so its points (a third
     # of the scan, +-2 cm of range noise) are near-boundary for both ranks:
     # observed 0.82 + 0.55 (mid360, 8 m tiles) and 0.64 + 0.57 (1 m voxels,

@@ -1,0 +1,575 @@
+// iekf.hip — the IEKF hot loop over the device-resident voxel map.
+//
+// SURVEY §8(a) rows:
+//   A7  match / OctoTree::match / inside  voxel_map.cpp:241-266, octree.cpp:551-595, 732-737
+//   A9  LioStateEstimation point loop     odometry.cpp:111-148
+#include <hipcub/hipcub.hpp>
+#include "vg_iekf.h"
+
+namespace vg {
+
+// ------------------------------------------------------------------ IEKF
+// One IEKF iteration's point loop (odometry.cpp:111-148): world covariance,
+// association (cached-leaf fast path or root hash + octree descent), the
+// probabilistic point-to-plane gate (octree.cpp:557-579), the Jacobian and the
+// weighted normal-equation accumulation. Each block writes 34 partial sums:
+// HTH (upper 21), HTz (6), nnt (upper 6), match count (1). fp64 throughout.
+__device__ __forceinline__ int descend(const NodeHdr* __restrict__ hdr, int node, const V3& w) {
+  for (int d = 0; d < 8 && node >= 0; d++) {
+    const NodeHdr& h = hdr[node];
+    if (h.octo == 0) return node;
+    node = h.child[octant(w, h.center)];
+  }
+  return -1;
+}
+
+// OctoTree::match at a leaf; returns 1 and sigma on success
+__device__ __forceinline__ int match_leaf(const NodeHdr& h, const PlaneRec& P, const V3& wld, const M3& var_wld,
+                                          double& sigma) {
+  if (!h.is_plane) return 0;
+  V3 c = ld_v3(P.center), n = ld_v3(P.normal);
+  V3 d = sub(wld, c);
+  float dis_to_plane = fabs(dot3(n, d));
+  V3 cw = sub(c, wld);
+  float dis_to_center = cw[0] * cw[0] + cw[1] * cw[1] + cw[2] * cw[2];
+  float range_dis = (dis_to_center - dis_to_plane * dis_to_plane);
+  if (!(range_dis <= 3 * 3 * P.radius)) return 0;
+  double J[6] = {d[0], d[1], d[2], -n[0], -n[1], -n[2]};
+  double t[6];
+  for (int j = 0; j < 6; j++) {
+    double s = J[0] * P.var[sym_idx(6, 0, j)];
+    for (int k = 1; k < 6; k++) s += J[k] * P.var[sym_idx(6, k, j)];
+    t[j] = s;
+  }
+  double sl = t[0] * J[0];
+  for (int j = 1; j < 6; j++) sl += t[j] * J[j];
+  V3 vn = mul(var_wld, n);
+  sl += dot3(n, vn);
+  if (dis_to_plane < 3 * sqrt(sl)) {
+    sigma = sl;
+    return 1;
+  }
+  return 0;
+}
+
+__device__ __forceinline__ bool inside(const NodeHdr& h, const V3& w) {
+  double hl = h.qlen * 2;
+  return (w[0] >= h.center[0] - hl && w[0] <= h.center[0] + hl && w[1] >= h.center[1] - hl &&
+          w[1] <= h.center[1] + hl && w[2] >= h.center[2] - hl && w[2] <= h.center[2] + hl);
+}
+
+
+// ---- wave sums without LDS: the partner across lane bit L (lane ^ L) via
+// gfx950's v_permlane32_swap / v_permlane16_swap and DPP (row_ror:8, row
+// shifts by 4, quad perms)
+__device__ __forceinline__ double pack_d(unsigned lo, unsigned hi) {
+  return __longlong_as_double(((long long)hi << 32) | lo);
+}
+template <int C>
+__device__ __forceinline__ unsigned dpp32(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, C, 0xf, 0xf, false);
+}
+template <int L>
+__device__ __forceinline__ double xor_lane(double v, int lane) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+  if constexpr (L == 32) {  // r[0] = x[lane % 32], r[1] = x[lane % 32 + 32]
+    auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return (lane & 32) ? pack_d(l2[0], h2[0]) : pack_d(l2[1], h2[1]);
+  } else if constexpr (L == 16) {  // r[0] = the even row's x, r[1] = the odd row's
+    auto l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return (lane & 16) ? pack_d(l2[0], h2[0]) : pack_d(l2[1], h2[1]);
+  } else if constexpr (L == 8) {
+    return pack_d(dpp32<0x128>(lo), dpp32<0x128>(hi));  // row_ror:8
+  } else if constexpr (L == 4) {
+    const double up = pack_d(dpp32<0x104>(lo), dpp32<0x104>(hi));  // row_shl:4 (lane i <- i + 4)
+    const double dn = pack_d(dpp32<0x114>(lo), dpp32<0x114>(hi));  // row_shr:4 (lane i <- i - 4)
+    return (lane & 4) ? dn : up;
+  } else if constexpr (L == 2) {
+    return pack_d(dpp32<0x4E>(lo), dpp32<0x4E>(hi));  // quad_perm [2,3,0,1]
+  } else {
+    return pack_d(dpp32<0xB1>(lo), dpp32<0xB1>(hi));  // quad_perm [1,0,3,2]
+  }
+}
+// one level of a halving wave sum: the lanes with bit L clear keep the first
+// ceil(N/2) values, the others the rest, each adding its partner's copy
+template <int L, int N>
+__device__ __forceinline__ void halve(const double (&v)[N], double (&w)[(N + 1) / 2], int lane, int& idx, int& n) {
+  constexpr int H = (N + 1) / 2;
+  const bool hi = (lane & L) != 0;
+#pragma unroll
+  for (int j = 0; j < H; j++) {
+    const double a = v[j], b = (H + j < N) ? v[H + j] : 0.0;
+    w[j] = (hi ? b : a) + xor_lane<L>(hi ? a : b, lane);
+  }
+  if (hi) {
+    idx += H;
+    n = n > H ? n - H : 0;
+  } else {
+    n = n < H ? n : H;
+  }
+}
+
+// The pose (x_curr R, p and the rotation / translation covariance blocks) is
+// read from the device state the previous k_iekf_update wrote; the kernel is a
+// no-op once the IEKF has finished (st->done). Iteration 0 ignores the leaf
+// cache (no association yet, odometry.cpp:111-132).
+// one IEKF iteration's point loop over the workgroup's chunk vb (k_iekf): the
+// 34 sums of this lane's points
+// kPf: a point whose cached leaf matched last iteration (octos[i]) touches its
+// plane record's 128 B lines right away, beside the header load, so the
+// gate's record reads hit in cache instead of a second dependent miss
+template <bool kPf = false>
+__device__ __forceinline__ void iekf_points(const MP& mp, const DState* __restrict__ st, const DevMap& m,
+                                            int* __restrict__ cache, int* __restrict__ pk, int it, int nb, int vb,
+                                            const M3& R, const V3& p, const M3& rot_var, const M3& tsl_var,
+                                            double (&acc)[kIekfVals]) {
+  const int* __restrict__ keep = iekf_keep(st);
+  const int n = keep ? st->snk : st->sn;
+  const float* __restrict__ x = st->sx;
+  const float* __restrict__ y = st->sy;
+  const float* __restrict__ z = st->sz;
+  const M3 Rt = tr(R);
+  for (int j = 0; j < kIekfVals; j++) acc[j] = 0.0;
+  for (int q = vb * blockDim.x + threadIdx.x; q < n; q += nb * blockDim.x) {
+    const int i = keep ? keep[q] : q;  // the raw index (the memo and the profiling pass are per raw point)
+    V3 pnt;
+    M3 var;
+    var_init_pt(mp, x[i], y[i], z[i], pnt, var);
+    M3 var_world = world_var(R, var, pnt, rot_var, tsl_var);
+    V3 wld = rigid(R, pnt, p);
+    // cache[i]: the leaf of the point's last match (the reference's octos[i],
+    // odometry.cpp:124-131, reset per scan) or, after a failed match, the
+    // leaf the descent reached — a memo only (bit 30 tags it): while the
+    // point stays inside that leaf's box and its float voxel key still names
+    // the leaf's root (the lookup rounds in float, voxel_map.cpp:246-253), the
+    // lookup would reach the same leaf, so unmatched points skip the hash +
+    // descent too
+    const int cv = it > 0 ? cache[i] : -1;
+    int leaf = cv >= 0 ? (cv & 0x3fffffff) : -1;
+    int flag = 0;
+    double sigma = 0;
+    double pf0 = 0.0, pf1 = 0.0, pf2 = 0.0;
+    if (kPf && cv >= 0 && !(cv & 0x40000000)) {  // bytes 0, 112, 216: every 128 B line the 224 B record spans
+      const double* rec = reinterpret_cast<const double*>(&m.pl[leaf]);
+      pf0 = rec[0];
+      pf1 = rec[14];
+      pf2 = rec[27];
+    }
+    // a matched leaf (octos[i]): OctoTree::inside's inclusive box; a memo: the
+    // descent's own region (dbox: strict where the descent is strict), so a
+    // point on a centre plane is never kept in the wrong sibling
+    bool hit = leaf >= 0 && ((cv & 0x40000000) ? in_dbox(m.dbox + (size_t)leaf * 6, wld) : inside(m.hdr[leaf], wld));
+    if (hit && (cv & 0x40000000)) {
+      uint64_t kw, kl;
+      const NodeHdr& hl = m.hdr[leaf];
+      hit = pack_key(wld, mp.vs, kw) && pack_key(v3(hl.center[0], hl.center[1], hl.center[2]), mp.vs, kl) && kw == kl;
+    }
+    if (hit) {
+      if (kPf) asm volatile("" ::"v"(pf0), "v"(pf1), "v"(pf2));  // the touches complete here, not before
+      flag = match_leaf(m.hdr[leaf], m.pl[leaf], wld, var_world, sigma);
+      if (!flag && !(cv & 0x40000000)) leaf = -2;  // the reference's octos[i] stays: keep the cache
+    } else {
+      leaf = -1;
+      uint64_t key;
+      if (pack_key(wld, mp.vs, key) && owns(m, key)) {  // another shard's tile: not matched here
+        int root = hash_find(m.hkey, m.hval, m.hash_mask, key);
+        int lf = root >= 0 ? descend(m.hdr, root, wld) : -1;
+        if (lf >= 0) {
+          flag = match_leaf(m.hdr[lf], m.pl[lf], wld, var_world, sigma);
+          leaf = lf;
+        }
+      }
+    }
+    if (pk) pk[i] = flag ? leaf : -1;  // the leaf whose plane this iteration read (profiling pass)
+    if (flag) {
+      cache[i] = leaf;
+    } else if (leaf >= 0) {
+      if (it == 0 || cv < 0 || (cv & 0x40000000)) cache[i] = leaf | 0x40000000;  // no octos[i] to keep
+    } else if (leaf == -1 && (it == 0 || cv < 0 || (cv & 0x40000000))) {
+      cache[i] = -1;
+    }
+    if (flag) {
+      const PlaneRec& P = m.pl[leaf];
+      V3 nn = ld_v3(P.normal), c = ld_v3(P.center);
+      double R_inv = 1.0 / (0.0005 + sigma);
+      double resi = dot3(nn, sub(wld, c));
+      V3 j3 = mul(mul(hat(pnt), Rt), nn);
+      double jac[6] = {j3[0], j3[1], j3[2], nn[0], nn[1], nn[2]};
+      int k = 0;
+      for (int r = 0; r < 6; r++) {
+        double jr_ = jac[r] * R_inv;
+        for (int c2 = r; c2 < 6; c2++, k++) acc[k] += jr_ * jac[c2];
+      }
+      for (int r = 0; r < 6; r++) acc[21 + r] -= jac[r] * (R_inv * resi);
+      acc[27] += nn[0] * nn[0];
+      acc[28] += nn[0] * nn[1];
+      acc[29] += nn[0] * nn[2];
+      acc[30] += nn[1] * nn[1];
+      acc[31] += nn[1] * nn[2];
+      acc[32] += nn[2] * nn[2];
+      acc[33] += 1.0;
+    }
+  }
+}
+// the workgroup's 34 sums (threads < 34 hold one each): a halving butterfly
+// per wave, then LDS across the 4 waves (fixed tree). Every level pairs lane ^
+// L for L = 32, 16, ..., 1, so each sum is bit for bit lane 0's of a shfl_down
+// tree, but a lane hands over half of the values it carries at every level:
+// 37 exchanges for the 34 sums instead of 204, through permlane / DPP
+__device__ __forceinline__ double iekf_wg_sum(double (&acc)[kIekfVals], double (*red)[kIekfVals]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  static_assert(kIekfVals == 34, "the halving levels below are laid out for 34 sums");
+  int ridx = 0, rn = kIekfVals;
+  double h17[17], h9[9], h5[5], h3[3], h2[2], h1[1];
+  halve<32>(acc, h17, lane, ridx, rn);
+  halve<16>(h17, h9, lane, ridx, rn);
+  halve<8>(h9, h5, lane, ridx, rn);
+  halve<4>(h5, h3, lane, ridx, rn);
+  halve<2>(h3, h2, lane, ridx, rn);
+  halve<1>(h2, h1, lane, ridx, rn);
+  if (rn == 1) red[wv][ridx] = h1[0];
+  __syncthreads();
+  const int j = threadIdx.x < kIekfVals ? threadIdx.x : 0;
+  return ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+}
+// the pose words an iteration's point loop reads from x_curr: R 9, p 3, the
+// rotation and translation covariance blocks 9 + 9
+__device__ __forceinline__ double pose_word(const double* xc, int t) {
+  if (t < 12) return xc[t];
+  if (t < 21) return xc[kXS + ((t - 12) / 3) * 15 + (t - 12) % 3];
+  return xc[kXS + (3 + (t - 21) / 3) * 15 + 3 + (t - 21) % 3];
+}
+__device__ __forceinline__ void pose_of(const double* w, M3& R, V3& p, M3& rot_var, M3& tsl_var) {
+  for (int q = 0; q < 9; q++) {
+    R[q] = w[q];
+    rot_var[q] = w[12 + q];
+    tsl_var[q] = w[21 + q];
+  }
+  p = v3(w[9], w[10], w[11]);
+}
+
+template <bool kPf>
+__global__ void __launch_bounds__(256) k_iekf(MP mp, DState* __restrict__ st, int it, DevMap m,
+                                              int* __restrict__ cache, double* __restrict__ partials,
+                                              int* __restrict__ pk) {
+  if (st->done) return;
+  // the scan's critical chain: its waves issue ahead of co-resident waves of
+  // the previous scan's margi remainder (k_margi_copy) on a shared SIMD
+  __builtin_amdgcn_s_setprio(2);
+  const bool clk_on = st->clk.on != 0;
+  const int clk_slot = (st->clk.scan * 4 + it) & (kClkRing - 1);
+  if (clk_on && blockIdx.x == 0 && threadIdx.x == 0) {
+    st->clk.t0[clk_slot] = (unsigned long long)wall_clock64();
+    st->clk.exec[clk_slot] = 1;
+  }
+  VG_PROBE_BEGIN();
+  double w[30];
+  for (int t = 0; t < 30; t++) w[t] = pose_word(st->xc, t);
+  M3 R, rot_var, tsl_var;
+  V3 p;
+  pose_of(w, R, p, rot_var, tsl_var);
+  // XCD-aware chunking (cdna_hip_programming.md T1): blocks are dealt
+  // round-robin over the 8 XCDs, so block b works on chunk (b % 8) * (nb / 8)
+  // + b / 8 — each XCD sweeps a contiguous run of the scan and the plane /
+  // node records of neighbouring points stay in its own L2 (nb % 8 == 0)
+  const int nb = gridDim.x;
+  const int vb = iekf_chunk(blockIdx.x, nb);
+  double acc[kIekfVals];
+  iekf_points<kPf>(mp, st, m, cache, pk, it, nb, vb, R, p, rot_var, tsl_var, acc);
+  if (blockIdx.x == 0 && threadIdx.x == 0) st->iekf_pts += iekf_n(st);  // (vg_stats::iekf_points)
+  if (blockIdx.x == 0) VG_PROBE_MARK(30);  // the point loop (thread 0 of block 0)
+  __shared__ double red[4][kIekfVals];
+  const double v = iekf_wg_sum(acc, red);
+  if (threadIdx.x < kIekfVals) partials[(size_t)blockIdx.x * kIekfVals + threadIdx.x] = v;
+  if (clk_on && blockIdx.x < kClkBlocks) {  // the workgroup's end (its partials written)
+    __syncthreads();
+    if (threadIdx.x == 0) st->clk.tend[clk_slot][blockIdx.x] = (unsigned long long)wall_clock64();
+  }
+  if (blockIdx.x == 0) VG_PROBE_MARK(31);  // the block reduction
+#ifdef VG_PROBE
+  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_probe[59], 1ull);
+#endif
+}
+
+// the IEKF's end to the insert's stream (vg_ctx::d_sync[1]): every thread's
+// state writes released at agent scope (one workgroup: one L2 write-back),
+// then the flag advances by one
+__device__ __forceinline__ void iekf_signal_done(unsigned* flag) {
+  if (!flag) return;
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// P_k of SURVEY 8(d), the profiling pass only: distinct plane records the
+// iteration read, deduplicated with a per-node tag (outside k_iekf's timing)
+__global__ void __launch_bounds__(256) k_iekf_planes(const DState* __restrict__ st, DevMap m,
+                                                     const int* __restrict__ pk, int tag, int* __restrict__ out) {
+  if (st->done) return;
+  const int* keep = iekf_keep(st);
+  const int n = iekf_n(st);
+  int cnt = 0;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
+    const int leaf = pk[keep ? keep[q] : q];
+    if (leaf >= 0 && m.stamp[leaf] != tag && atomicExch(&m.stamp[leaf], tag) != tag) cnt++;
+  }
+  wave_append(out, cnt);
+}
+
+// The IEKF update of iteration `it` (vg_iekf.h) as its own one-workgroup
+// launch. (A last-workgroup-done ticket inside k_iekf would need an
+// agent-scope release per workgroup, which on the multi-XCD MI355X writes back
+// the XCD's L2 each time: measured ~20 us per iteration, far more than the
+// launch it saves.)
+// done_flag: the update that finishes the IEKF also advances the IEKF ->
+// insert hand-off flag (one workgroup: one release), so no k_sync_set launch
+// follows the IEKF graph
+__global__ void __launch_bounds__(1024) k_iekf_update(int nb, const double* __restrict__ partials,
+                                                     DState* __restrict__ st, int it, unsigned* done_flag,
+                                                     int xworld, int* xerr) {
+  __shared__ IekfLds L;
+  if (st->done) return;
+  __builtin_amdgcn_s_setprio(2);  // (k_iekf)
+  iekf_update_block(nb, partials, st, it, L, xworld, xerr);
+  if (done_flag && L.fin) iekf_signal_done(done_flag);
+}
+// sharded mode: this shard's 34 sums (the update then runs on the all-reduced ones)
+// sharded mode: this shard's 34 sums, packed into the exchange frame (the
+// update runs on the all-reduced frame, k_iekf_update checks its guard); an
+// iteration after convergence still closes the frame (the exchange runs)
+__global__ void __launch_bounds__(1024) k_iekf_reduce(int nb, const double* __restrict__ partials,
+                                                     const DState* __restrict__ st, XchgArg xa) {
+  __shared__ IekfLds L;
+  const bool done = st->done;
+  if (!done) {
+    const int n = iekf_n(st);
+    iekf_reduce_block(nb, partials, L, n < nb * 256 ? (n + 255) / 256 : nb);
+  }
+  for (int i = threadIdx.x; i < xa.n - 2; i += blockDim.x) xa.frame[i] = (!done && i < kIekfVals) ? L.o[i] : 0.0;
+  if (threadIdx.x == 0) xchg_close(xa.frame, xa.n, 0, xa.seq);
+}
+
+// grid of the IEKF point loop: sized by the context's capacity (the kernels
+// read the scan size from the device state), a multiple of the 8 XCDs
+static int iekf_blocks(vg_ctx* ctx) {
+  return ((grid_for(ctx->cap.max_points_per_scan, 256, 512) + 7) / 8) * 8;
+}
+int iekf_grid(vg_ctx* ctx) { return iekf_blocks(ctx); }
+
+// one IEKF iteration: the point loop (block partials) and the update; the
+// optional event pair brackets k_iekf alone (vg_profile)
+int iekf_iteration(vg_ctx* ctx, const MP& mp, const float* x, const float* y, const float* z, int n, int it,
+                   hipEvent_t ev0, hipEvent_t ev1, int tag, hipStream_t s, unsigned* done_flag) {
+  Work& w = ctx->wk;
+  if (!s) s = ctx->stream;
+  (void)x;
+  (void)y;
+  (void)z;
+  (void)n;  // the scan is read from the device state (state_set_scan)
+  const int nb = iekf_blocks(ctx);
+  if (ev0) VG_HIP(hipEventRecord(ev0, s));
+  auto kern = ctx->iekf_prefetch ? k_iekf<true> : k_iekf<false>;
+  kern<<<nb, 256, 0, s>>>(mp, ctx->st, it, ctx->map, w.iekf_cache, w.partials, tag ? w.pk_leaf : nullptr);
+  if (ev1) VG_HIP(hipEventRecord(ev1, s));
+  if (tag) k_iekf_planes<<<nb, 256, 0, s>>>(ctx->st, ctx->map, w.pk_leaf, tag, &ctx->st->planes[it]);
+  if (sharded(ctx)) {  // this shard's sums packed into the frame, all-reduced, then the (replicated) update
+    Shard& sh = ctx->shard;
+    const XchgArg xa{sh.d_frame, sh.d_seq, ctx->map.counters + kCntErr, kShardSmall, sh.world};
+    k_iekf_reduce<<<1, 1024, 0, s>>>(nb, w.partials, ctx->st, xa);  // (the unsharded update's 60 row groups)
+    VG_TRY(shard_exchange(ctx, kShardSmall, s));
+    k_iekf_update<<<1, 1024, 0, s>>>(-1, sh.d_frame, ctx->st, it, nullptr, sh.world, ctx->map.counters + kCntErr);
+  } else {
+    k_iekf_update<<<1, 1024, 0, s>>>(nb, w.partials, ctx->st, it, done_flag, 0, nullptr);
+  }
+  VG_HIP(hipGetLastError());
+  return VG_OK;
+}
+
+// ---- sharded mode (world > 1): the scan's points this rank can match ----
+// A point is matched only in its own root voxel (A7, voxel_map.cpp:241-266),
+// and only the owner of the voxel's tile holds it. At the
+// scan's opening pose each raw point's world position w is taken with a box of
+// kKeepM metres around it; the key rule is monotone in each coordinate, so
+// the voxel keys of the box are those between the keys of w - kKeepM and
+// w + kKeepM, and the point is kept when a tile of those keys is this rank's:
+// one pass and a prefix sum per scan, and the IEKF's four iterations then
+// transform and test only those (DState::skeep). The list holds while every
+// point moved less than kmargin = kKeepM since the opening (iekf_keep, checked
+// per iteration on the device), else the iteration takes every point. owns()
+// still decides per point and iteration, so the matches are the unsharded
+// path's either way; only the order of the fp sums within a rank follows the
+// list.
+constexpr double kKeepM = 0.1;
+__global__ void __launch_bounds__(256) k_keep_flags(MP mp, const DState* __restrict__ st, DevMap m,
+                                                    int* __restrict__ flag, unsigned* __restrict__ rmax_bits) {
+  const int n = st->sn;
+  const float* __restrict__ x = st->sx;
+  const float* __restrict__ y = st->sy;
+  const float* __restrict__ z = st->sz;
+  M3 R;
+  for (int q = 0; q < 9; q++) R[q] = st->xc[q];
+  const V3 p = v3(st->xc[9], st->xc[10], st->xc[11]);
+  const M3 eR = ld_m3(mp.extR);
+  const V3 et = ld_v3(mp.extt);
+  float rmax = 0.0f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const V3 pnt = rigid(eR, v3(x[i], y[i], z[i]), et);
+    const V3 w = rigid(R, pnt, p);
+    rmax = fmaxf(rmax, (float)norm3(pnt));
+    int64_t lo[3], hi[3];
+    bool in = true;
+    for (int j = 0; j < 3; j++) {
+      const int64_t k0 = key_axis_d(w[j] - kKeepM, mp.vs) + kKeyOff, k1 = key_axis_d(w[j] + kKeepM, mp.vs) + kKeyOff;
+      lo[j] = (k0 > 0 ? k0 : 0) >> 4;  // (keys outside the packed range are never matched)
+      hi[j] = (k1 < 2 * kKeyOff - 1 ? k1 : 2 * kKeyOff - 1) >> 4;
+      in &= k1 >= 0 && k0 < 2 * kKeyOff;
+    }
+    int keep = 0;
+    if (in)
+      for (int64_t tx = lo[0]; tx <= hi[0] && !keep; tx++)
+        for (int64_t ty = lo[1]; ty <= hi[1] && !keep; ty++)
+          for (int64_t tz = lo[2]; tz <= hi[2] && !keep; tz++)
+            keep = tile_owner_t((uint64_t)tx, (uint64_t)ty, (uint64_t)tz, m.shard_world) == m.shard_rank;
+    flag[i] = keep;
+  }
+  for (int off = 32; off > 0; off >>= 1) rmax = fmaxf(rmax, __shfl_down(rmax, off, 64));
+  if ((threadIdx.x & 63) == 0) atomicMax(rmax_bits, __float_as_uint(rmax));  // (non-negative: ordered as bits)
+}
+__global__ void __launch_bounds__(256) k_keep_scatter(MP mp, DState* __restrict__ st, const int* __restrict__ flag,
+                                                      const int* __restrict__ pos, int* __restrict__ list,
+                                                      const unsigned* __restrict__ rmax_bits) {
+  const int n = st->sn;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    if (flag[i]) list[pos[i]] = i;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->snk = n > 0 ? pos[n - 1] + flag[n - 1] : 0;
+    st->skeep = list;
+    for (int t = 0; t < 12; t++) st->kpose[t] = st->xc[t];
+    st->krmax = (double)__uint_as_float(*rmax_bits) * (1.0 + 1e-6) + 1e-6;  // (the float max rounded up)
+    st->kmargin = kKeepM;
+  }
+}
+static int keep_list(vg_ctx* ctx, const MP& mp, int n, hipStream_t s) {
+  Shard& sh = ctx->shard;
+  if (n <= 0) n = 1;  // (an empty scan: the kernels read the count from the state)
+  VG_HIP(hipMemsetAsync(sh.keep_rmax, 0, sizeof(unsigned), s));
+  const int g = grid_for(n);
+  k_keep_flags<<<g, kBlock, 0, s>>>(mp, ctx->st, ctx->map, sh.keep_flag, sh.keep_rmax);
+  size_t tb = sh.keep_tmp_bytes;
+  VG_HIP(hipcub::DeviceScan::ExclusiveSum(sh.keep_tmp, tb, sh.keep_flag, sh.keep_pos, n, s));
+  k_keep_scatter<<<g, kBlock, 0, s>>>(mp, ctx->st, sh.keep_flag, sh.keep_pos, sh.keep_list, sh.keep_rmax);
+  VG_HIP(hipGetLastError());
+  return VG_OK;
+}
+
+// the four IEKF iterations (odometry.cpp:68). The launches do not change from
+// scan to scan, so an unsharded context captures them once and replays the
+// graph: one host call instead of eight launches, and the device starts each
+// node without the per-launch dispatch gap. The per-stage profiling pass
+// (vg_profile bit 1) launches directly, with an event pair around each k_iekf.
+int iekf_run(vg_ctx* ctx, const MP& mp, const float* x, const float* y, const float* z, int n, int bank,
+             const double* begin_xc, hipStream_t s, const PropArg* begin_prop, bool signal, bool* signalled,
+             bool opened) {
+  if (!s) s = ctx->stream;
+  if (signalled) *signalled = false;
+  if (begin_xc || begin_prop)  // the scan opens here (pipeline.cpp)
+    VG_TRY(state_scan_begin(ctx, begin_xc, x, y, z, n, s, begin_prop));
+  else if (!opened) VG_TRY(state_set_scan(ctx, x, y, z, n, s));
+  if (sharded(ctx) && ctx->shard.world > 1) VG_TRY(keep_list(ctx, mp, n, s));  // at the opening pose
+  const bool graph = ctx->use_graphs && !sharded(ctx) && !ctx->prof_stages;
+  const bool ev = ctx->prof_on && !graph;
+  // the last update signals the hand-off itself (k_iekf_update; not when sharded)
+  const bool self_signal = signal && !sharded(ctx);
+  unsigned* flag = self_signal ? ctx->d_sync + 1 : nullptr;
+  auto enqueue = [&]() -> int {
+    for (int it = 0; it < 4; it++)
+      VG_TRY(iekf_iteration(ctx, mp, x, y, z, n, it, ev ? ctx->iekf_ev[bank + it][0] : nullptr,
+                            ev ? ctx->iekf_ev[bank + it][1] : nullptr,
+                            graph || !ctx->prof_stages ? 0 : ++ctx->plane_tag, s, flag));
+    return VG_OK;
+  };
+  if (!graph) {
+    VG_TRY(enqueue());
+    if (signalled) *signalled = self_signal;
+    return VG_OK;
+  }
+  hipGraphExec_t& ge = ctx->g_iekf[self_signal ? 3 : 0];
+  if (!ge) {
+    std::lock_guard<std::recursive_mutex> cap_lk_(capture_mutex());  // (vg_internal.h)
+    VG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int r = enqueue();
+    hipGraph_t g = nullptr;
+    const hipError_t e = hipStreamEndCapture(s, &g);
+    if (r != VG_OK) return r;
+    VG_HIP(e);
+    VG_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    VG_HIP(hipGraphDestroy(g));
+  }
+  VG_HIP(hipGraphLaunch(ge, s));
+  if (signalled) *signalled = self_signal;
+  return VG_OK;
+}
+
+// Test-only (vgx_memo_probe): the IEKF memo at centre planes. For every
+// internal node, points exactly on its centre plane along each axis (the
+// other two coordinates at +-hl/2) are looked up afresh (hash + descent, the
+// reference's path: voxel_map.cpp:241-266, octree.cpp:586) and through the
+// memo of the same point one ulp above / below the plane (the previous
+// iteration's leaf). out: [0] samples, [1] memo != descent with the
+// inclusive box (OctoTree::inside), [2] memo != descent with the descent's
+// region (dbox, what k_iekf uses), [3] samples whose memo leaf differs from
+// the fresh one (the plane really separates two leaves).
+__global__ void __launch_bounds__(256) k_memo_probe(MP mp, DevMap m, int* __restrict__ out) {
+  const int nn = m.counters[kCntNodes];
+  int cnt[4] = {0, 0, 0, 0};
+  for (int node = blockIdx.x * blockDim.x + threadIdx.x; node < nn; node += gridDim.x * blockDim.x) {
+    const NodeHdr& h = m.hdr[node];
+    if (h.octo != 1) continue;
+    const double hl = h.qlen * 2;
+    for (int j = 0; j < 3; j++)
+      for (int sgn = 0; sgn < 4; sgn++)
+        for (int side = 0; side < 2; side++) {
+          V3 w = v3(h.center[0], h.center[1], h.center[2]);
+          int k1 = (j + 1) % 3, k2 = (j + 2) % 3;
+          w[k1] += ((sgn & 1) ? 0.5 : -0.5) * hl;
+          w[k2] += ((sgn & 2) ? 0.5 : -0.5) * hl;
+          V3 w2 = w;
+          w2[j] = nextafter(w[j], side ? 1e300 : -1e300);
+          uint64_t key, key2;
+          if (!pack_key(w, mp.vs, key) || !pack_key(w2, mp.vs, key2) || key != key2) continue;
+          const int root = hash_find(m.hkey, m.hval, m.hash_mask, key);
+          if (root < 0) continue;
+          const int fresh = descend(m.hdr, root, w), memo = descend(m.hdr, root, w2);
+          if (fresh < 0 || memo < 0) continue;
+          uint64_t kl;
+          const NodeHdr& hm = m.hdr[memo];
+          const bool same_root = pack_key(v3(hm.center[0], hm.center[1], hm.center[2]), mp.vs, kl) && kl == key;
+          const int p_old = (same_root && inside(hm, w)) ? memo : fresh;
+          const int p_new = (same_root && in_dbox(m.dbox + (size_t)memo * 6, w)) ? memo : fresh;
+          cnt[0]++;
+          cnt[1] += p_old != fresh;
+          cnt[2] += p_new != fresh;
+          cnt[3] += memo != fresh;
+        }
+  }
+  for (int k = 0; k < 4; k++)
+    if (cnt[k]) atomicAdd(&out[k], cnt[k]);
+}
+int map_memo_probe(vg_ctx* ctx, const MP& mp, int* out) {
+  int* dout = reinterpret_cast<int*>(ctx->wk.partials);  // scratch: the probe runs between scans
+  VG_HIP(hipMemsetAsync(dout, 0, 4 * sizeof(int), ctx->stream));
+  k_memo_probe<<<256, 256, 0, ctx->stream>>>(mp, ctx->map, dout);
+  VG_HIP(hipGetLastError());
+  VG_HIP(hipMemcpyAsync(out, dout, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VG_HIP(hipStreamSynchronize(ctx->stream));
+  return VG_OK;
+}
+
+}  // namespace vg
+
+#ifdef VG_PROBE
+VG_PROBE_READER(vg_probe_read_iekf)
+#endif

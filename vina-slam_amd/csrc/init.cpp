@@ -13,7 +13,7 @@
 // with the steady state's kernels — the deskew, the 0.5 m downsample and the
 // kd-tree IEKF point passes (kdlio.hip), down_sampling_close (downsample.hip),
 // motion_blur's per-point transform (state.hip k_blur_init), the map rebuild of
-// every round (map.hip: the insert with precomputed body points, the recut with
+// every round (insert.hip with precomputed body points, recut.hip with
 // the initialisation thresholds) and the LiDAR factor Hessian / residual
 // passes of the gravity LM (ba.hip). The host keeps what is O(IMU samples) or
 // O(window): the IMU means, the IMU pose integration, the preintegration, the

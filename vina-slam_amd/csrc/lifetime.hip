@@ -6,7 +6,7 @@
 // octree.cpp:597-608) and frees a leaf's point_fix once it reaches max_points
 // (octree.cpp:467-468); its heap takes the memory back. The device map is a
 // node pool with a bump counter and a point_fix arena with bump-allocated
-// blocks (a growing leaf abandons its old block, map.hip k_margi_leaf), so the
+// blocks (a growing leaf abandons its old block, margi.hip k_margi_leaf), so the
 // release here is: mark the erased roots (a root hash pass), mark every node by
 // its root (parent hops), then compact the pool and the arena in place,
 // order-preserving (an exclusive scan of the live flags is the new id of every

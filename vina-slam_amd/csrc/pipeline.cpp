@@ -874,7 +874,7 @@ int stage_recut(vg_ctx* ctx, int* nf_out) {
   if (!nf_out && P->win_count >= c.win_size && c.if_BA == 1) {
     // the LM follows: its kernels read the factor count on the device, and the
     // host learns the recut's outcome only once the LM is enqueued (stage_ba);
-    // sharded, the status is all-reduced first (map.hip k_pub_rc), so every
+    // sharded, the status is all-reduced first (recut.hip k_pub_rc), so every
     // rank takes the same host-sized completion and LM rerun
     P->rc_seq = ++ctx->rc_pub;  // the device counts its asynchronous recuts the same way (k_fac_sort)
     VG_TRY(map_recut(ctx, P->mpd, wa, c.thread_num, &nf, false, 1));

@@ -1,6 +1,6 @@
 // shard.hip — spatial-tile sharding of one sequence across contexts (one per
-// GPU): the collective transport behind the exchange points of map.hip / ba.hip
-// (SURVEY §8(e)). Two transports:
+// GPU): the collective transport behind the exchange points of iekf.hip /
+// insert.hip / recut.hip / ba.hip. Two transports:
 //   RCCL  ncclAllReduce on the context stream (stream-ordered, no host sync);
 //         `ncclComm_t` lives in the context.
 //   host  a caller-supplied in-place host all-reduce (e.g. torch.distributed

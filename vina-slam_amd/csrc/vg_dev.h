@@ -80,7 +80,7 @@ __host__ __device__ __forceinline__ int tile_owner_t(uint64_t tx, uint64_t ty, u
 __host__ __device__ __forceinline__ int tile_owner(uint64_t key, int world) {
   return tile_owner_t((key >> 46) & 0x1ffff, (key >> 25) & 0x1ffff, (key >> 4) & 0x1ffff, world);
 }
-// Sharded mode's keep list (DState::skeep, map.hip k_keep_*): usable while the
+// Sharded mode's keep list (DState::skeep, iekf.hip k_keep_*): usable while the
 // current pose x_curr moved every point by less than kmargin from the pose the
 // list was made at — |dR|_2 r_max + |dp| bounds |R q + p - (R0 q + p0)| for
 // |q| <= r_max, and for two rotations |R - R0|_2 = |R - R0|_F / sqrt(2) (the

@@ -1,5 +1,5 @@
 // vg_iekf.h — the IEKF update (odometry.cpp:192-254) as a workgroup-level
-// device routine, run by k_iekf_update after each k_iekf point loop (map.hip).
+// device routine, run by k_iekf_update after each k_iekf point loop (iekf.hip).
 //
 // The reference forms K_1 = (H_T_H + cov^-1)^-1 with two 15 x 15 inverses
 // (odometry.cpp:82, 194) but only ever uses its first six columns (K_1.block<15,6>,

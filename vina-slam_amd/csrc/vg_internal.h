@@ -199,7 +199,7 @@ struct Work {
   double* partials = nullptr;  // reduction partials
   int* iekf_cache = nullptr;   // per raw point cached leaf
   int* pk_leaf = nullptr;      // per raw point leaf read by the profiled IEKF iteration (P_k count)
-  int* rc = nullptr;           // device-side level counts (recut / margi, map.hip kRc*)
+  int* rc = nullptr;           // device-side level counts (recut / margi, vg_dev.h kRc*)
   uint32_t* cand_bits = nullptr;  // factor candidates of an asynchronous recut, one bit per node id
   int* plan = nullptr;         // per-leaf point_fix copy plan (margi)
   // the recut's odd levels: subdividing leaves, rcinfo, events (even levels: list2, v1, k0)
@@ -296,7 +296,7 @@ struct DState {
   double imurec[kMaxWin * kBaImuRec];
   KClock clk;
   // sharded mode (world > 1): the scan's points this rank can match, made
-  // once per scan at the opening pose (map.hip k_keep_*): raw indices,
+  // once per scan at the opening pose (iekf.hip k_keep_*): raw indices,
   // ascending; null: every point. The IEKF uses the list while the pose
   // stays within kmargin of kpose for every point (|dR|_F krmax + |dp|).
   const int* skeep;
@@ -349,7 +349,7 @@ struct Shard {
   int frame_n = 0;           // doubles per exchange (shard.hip: payload + guard pair)
   double* d_frame = nullptr; // the exchange frame (+ this rank's guard value)
   unsigned* d_seq = nullptr; // the device's count of exchanges (the guard's sequence number)
-  // the scan's kept points (world > 1, map.hip k_keep_*): per raw point its
+  // the scan's kept points (world > 1, iekf.hip k_keep_*): per raw point its
   // flag and exclusive prefix, the kept list, max |pnt| (float bits), scan scratch
   int *keep_flag = nullptr, *keep_pos = nullptr, *keep_list = nullptr;
   unsigned* keep_rmax = nullptr;
@@ -414,9 +414,9 @@ struct vg_ctx {
   hipEvent_t ev_tail_a = nullptr, ev_iekf_done = nullptr;
   bool tail_a_valid = false;  // ev_tail_a marks the latest main-stream work the next IEKF depends on
   hipEvent_t ev_scan_ready = nullptr;  // deskew done (row f1)
-  // the IEKF's 8 launches captured once and replayed (map.hip iekf_run)
+  // the IEKF's 8 launches captured once and replayed (iekf.hip iekf_run)
   hipGraphExec_t g_iekf[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] the four iterations, [3] the same, signalling the insert ([1], [2] unused)
-  hipGraphExec_t g_margi[4] = {};  // margi after the window view (map.hip map_margi): [gated + 2 * signalling]
+  hipGraphExec_t g_margi[4] = {};  // margi after the window view (margi.hip map_margi): [gated + 2 * signalling]
   hipGraphExec_t g_ba = nullptr;     // one LM iteration (ba.hip ba_run)
   hipGraphExec_t g_ba2 = nullptr;    // the first two LM iterations
   hipGraphExec_t g_ds = nullptr;     // the per-scan downsample chain (downsample.hip ds_enqueue_hashed)
@@ -444,8 +444,8 @@ struct vg_ctx {
   int ba_seq0_pre = 0;      // the LM flag numbers a scan graph's k_ba_init uses (ba_run pre > 0)
   bool ba_no_defer = false; // set by stage_ba's prefix step when the recut needs the host (no deferral)
   unsigned rc_flag_ctr = 0, pre_flag_ctr = 0;  // d_sync[3] / d_sync[4] values (scan graph hand-offs)
-  bool pool_zeroed = false;
-  bool ins_ev_pending = false;  // ev_ds_free / ev_recut_done of the last insert+recut graph not recorded yet  // map_reset has cleared the node records once (then only the used ids)
+  bool pool_zeroed = false;  // map_reset has cleared the node records once (then only the used ids)
+  bool ins_ev_pending = false;  // ev_ds_free / ev_recut_done of the last insert+recut graph not recorded yet
   bool use_graphs = true;  // margi prefix on the second stream
   bool overlap_iekf = true;  // the next IEKF under the margi remainder (lio_state_estimation)
   int pub_flags = 0;         // vg_set_publish: bit 0 = /map_cmap after each window BA (k_local_map)
@@ -684,6 +684,7 @@ inline hipError_t flush_insert_events(vg_ctx* ctx) {
   return hipEventRecord(ctx->ev_recut_done, ctx->stream);
 }
 int map_reset(vg_ctx* ctx);
+// iekf.hip
 int iekf_iteration(vg_ctx* ctx, const MP& mp, const float* x, const float* y, const float* z, int n, int it,
                    hipEvent_t ev0, hipEvent_t ev1, int tag = 0, hipStream_t s = nullptr,
                    unsigned* done_flag = nullptr);
@@ -696,7 +697,9 @@ int iekf_iteration(vg_ctx* ctx, const MP& mp, const float* x, const float* y, co
 int iekf_run(vg_ctx* ctx, const MP& mp, const float* x, const float* y, const float* z, int n, int bank,
              const double* begin_xc = nullptr, hipStream_t s = nullptr, const PropArg* begin_prop = nullptr,
              bool signal = false, bool* signalled = nullptr, bool opened = false);  // opened: scan already bound
-constexpr int kNeedInsertReplay = 1;  // map_recut: the insert overflowed k_ins_alloc, replay it first
+int iekf_grid(vg_ctx* ctx);  // k_iekf's workgroups (iekf.hip iekf_blocks)
+int map_memo_probe(vg_ctx* ctx, const MP& mp, int* out);  // test-only (vgx_memo_probe)
+// insert.hip
 // the initialisation's insert source (cut_voxel, initialization.cpp:229-246):
 // n fp64 body points, the kXC pose/covariance block of x_buf[i], both device
 struct InsPre {
@@ -710,17 +713,14 @@ struct InsPre {
 int map_insert(vg_ctx* ctx, const MP& mp, int slot, int n, int epoch, int thread_num, const PushArg* push = nullptr,
                const InsPre* pre = nullptr, const int* nd = nullptr);
 int map_insert_replay(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_num);
+// recut.hip
+constexpr int kNeedInsertReplay = 1;  // map_recut: the insert overflowed k_ins_alloc, replay it first
 int map_recut(vg_ctx* ctx, const MP& mp, const WinArg& wa, int thread_num, int* n_factors, bool replay = false,
               int pub_seq = 0);
 int map_recut_resume(vg_ctx* ctx, const MP& mp, int* n_factors);
-int map_set_attrs(vg_ctx* ctx);
-const int* map_rc_status(vg_ctx* ctx);
-int map_factor_finish(vg_ctx* ctx);  // k_factor_finish_dev when no k_ba_init took it (map.hip)  // the asynchronous recut's status word (k_fac_sort)
-int map_memo_probe(vg_ctx* ctx, const MP& mp, int* out);  // test-only (vgx_memo_probe)
-int iekf_grid(vg_ctx* ctx);  // k_iekf's workgroups (map.hip iekf_blocks)
-int sync_set(vg_ctx* ctx, hipStream_t s, int k, unsigned value, const int* gate = nullptr);  // state.hip: cross-stream flags
-int sync_wait(vg_ctx* ctx, hipStream_t s, int k, unsigned target);
-int sync_wait_dev(vg_ctx* ctx, hipStream_t s, int k, const int* target, const int* gate);  // target / gate on the device
+const int* map_rc_status(vg_ctx* ctx);  // the asynchronous recut's status word (k_fac_sort)
+int map_factor_finish(vg_ctx* ctx);  // k_factor_finish_dev when no k_ba_init took it
+// margi.hip
 // multi_margi + the device-state slide; publishes the state (pub_seq, before
 // the margi kernels) and the end-of-scan counters (pub_seq2)
 // flags (the scan graph): {recut-done value of d_sync[3] to wait for, value to
@@ -731,6 +731,9 @@ int map_margi(vg_ctx* ctx, const MP& mp, const WinArg& wa, int n_oldest, int thr
               const int* gate);
 int map_margi_tail_capture(vg_ctx* ctx, const MP& mp, const WinArg& wa);  // the scan graph's gated margi tail
 // state.hip
+int sync_set(vg_ctx* ctx, hipStream_t s, int k, unsigned value, const int* gate = nullptr);  // cross-stream flags
+int sync_wait(vg_ctx* ctx, hipStream_t s, int k, unsigned target);
+int sync_wait_dev(vg_ctx* ctx, hipStream_t s, int k, const int* target, const int* gate);  // target / gate on the device
 int state_alloc(vg_ctx* ctx);
 // x_curr / x_prop / IEKF flags; with x != nullptr also the scan the IEKF reads
 // prop: propagate on the device (k_scan_prop), optionally waiting inside for

@@ -1023,7 +1023,7 @@ extern "C" int vgx_debug(vg_ctx* ctx, int key, int value) {
 }
 
 // Test-only: the IEKF memo against fresh descents at internal nodes' centre
-// planes (map.hip k_memo_probe); out[4]: samples, mismatches of the inclusive
+// planes (iekf.hip k_memo_probe); out[4]: samples, mismatches of the inclusive
 // box, mismatches of the descent region k_iekf uses, samples split by the plane
 extern "C" int vgx_memo_probe(vg_ctx* ctx, int* out) {
   if (!ctx || !out) return VG_E_ARG;
