@@ -568,6 +568,48 @@ int map_memo_probe(vg_ctx* ctx, const MP& mp, int* out) {
   return VG_OK;
 }
 
+// Test-only (vgx_iekf_update): one k_iekf_update launch, as an IEKF iteration
+// makes it, on given block partials (nb >= 0: nb x kIekfVals through the
+// ordered reduction; nb < 0: the 34 final sums), states (250-double IMUST
+// layout), iteration and rematch count. The device state's x_curr, x_prop, sn,
+// rematch and done are overwritten, so use a context that is not stepped
+// afterwards. x_out: x_curr after the update; G6_out (96 doubles): G(:, 0:6)
+// 15 x 6 row-major, then the six nnt sums; flags_out: iters, matches[it],
+// rematch, done.
+int iekf_update_test(vg_ctx* ctx, int nb, const double* partials, int n_points, const double* x_curr,
+                     const double* x_prop, int it, int rematch, double* x_out, double* G6_out, int* flags_out) {
+  Work& w = ctx->wk;
+  if (sharded(ctx) || it < 0 || it > 3 || nb == 0 || nb > w.nparts || n_points < 0 || rematch < 0) {
+    ctx->err = "vgx_iekf_update: bad argument";
+    return VG_E_ARG;
+  }
+  hipStream_t s = ctx->stream;
+  DState* st = ctx->st;
+  const size_t np = (nb < 0 ? 1 : (size_t)nb) * kIekfVals;
+  const int zero = 0;
+  VG_HIP(hipMemcpy(w.partials, partials, np * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(st->xc, x_curr + 1, kXC * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(st->xp, x_prop + 1, kXC * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(&st->sn, &n_points, sizeof(int), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(&st->rematch, &rematch, sizeof(int), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(&st->done, &zero, sizeof(int), hipMemcpyHostToDevice));
+  VG_HIP(hipDeviceSynchronize());  // (the context's stream does not wait for the null stream)
+  k_iekf_update<<<1, 1024, 0, s>>>(nb, w.partials, st, it, nullptr, 0, nullptr);
+  VG_HIP(hipGetLastError());
+  VG_HIP(hipStreamSynchronize(s));
+  int ints[9];  // it, rematch, done, iters, degenerate, matches[4]
+  x_out[0] = x_curr[0];
+  VG_HIP(hipMemcpy(x_out + 1, st->xc, kXC * sizeof(double), hipMemcpyDeviceToHost));
+  VG_HIP(hipMemcpy(G6_out, st->G6, 90 * sizeof(double), hipMemcpyDeviceToHost));
+  VG_HIP(hipMemcpy(G6_out + 90, st->nnt, 6 * sizeof(double), hipMemcpyDeviceToHost));
+  VG_HIP(hipMemcpy(ints, &st->it, sizeof(ints), hipMemcpyDeviceToHost));
+  flags_out[0] = ints[3];
+  flags_out[1] = ints[5 + it];
+  flags_out[2] = ints[1];
+  flags_out[3] = ints[2];
+  return VG_OK;
+}
+
 }  // namespace vg
 
 #ifdef VG_PROBE

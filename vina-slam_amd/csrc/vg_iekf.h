@@ -148,16 +148,36 @@ __device__ __forceinline__ void iekf_update_tail(DState* __restrict__ st, int it
   if (tid < 64) {  // K6 = cov(:, 0:6) M^-1, M = I + HTH cov66: solve M^T X = cov(:, 0:6)^T, K6 = X^T
     const int lane = tid;
     const double* cov = st->xc + kXS;
+    // The system is solved in the covariance's own units: with D = diag(d),
+    // d_l the power of two nearest below sqrt(cov_ll), D M D^-1 = I + (D HTH D)
+    // (D^-1 cov66 D^-1) and K6 = (cov(:, 0:6) D^-1) (D M D^-1)^-1 D. Powers of
+    // two scale exactly, so nothing changes while the pivots stay the same (in
+    // particular for rotation and position variances of one scale); with the
+    // blocks decades apart the unscaled rows made partial pivoting pick poor
+    // pivots (G's position rows 400 x less accurate than the two-inverse route
+    // at sum R_inv = 1e12, tests/test_iekf_update_gpu.py).
+    auto half_exp = [&](int l) {  // (a variance that is not positive and finite is left unscaled)
+      const double c = cov[l * 15 + l];
+      return (c > 0.0 && c < 1.7e308) ? (ilogb(c) >> 1) : 0;
+    };
+    double d[6], dinv[6];
+#pragma unroll
+    for (int l = 0; l < 6; l++) {
+      const int e = half_exp(l);
+      d[l] = ldexp(1.0, e);
+      dinv[l] = ldexp(1.0, -e);
+    }
     double col[6];
-    if (lane < 6) {  // column `lane` of M^T = row `lane` of M
+    if (lane < 6) {  // column `lane` of (D M D^-1)^T = row `lane` of D M D^-1
+      const double dl = ldexp(1.0, half_exp(lane));
       for (int r = 0; r < 6; r++) {
         double sm = hth(lane, 0) * cov[0 * 15 + r];
         for (int l = 1; l < 6; l++) sm += hth(lane, l) * cov[l * 15 + r];
-        col[r] = ((lane == r) ? 1.0 : 0.0) + sm;
+        col[r] = ((lane == r) ? 1.0 : 0.0) + (sm * dl) * dinv[r];
       }
     } else {
-      const int i = lane < 21 ? lane - 6 : 0;  // column i of cov(:, 0:6)^T = row i of cov, cols 0..5
-      for (int r = 0; r < 6; r++) col[r] = cov[i * 15 + r];
+      const int i = lane < 21 ? lane - 6 : 0;  // column i of (cov(:, 0:6) D^-1)^T = row i of cov, cols 0..5
+      for (int r = 0; r < 6; r++) col[r] = cov[i * 15 + r] * dinv[r];
     }
 #pragma unroll
     for (int c = 0; c < 6; c++) {
@@ -190,6 +210,10 @@ __device__ __forceinline__ void iekf_update_tail(DState* __restrict__ st, int it
 #pragma unroll
       for (int r = 0; r < 6; r++)
         if (r != c && pc[r] != 0.0) col[r] -= pc[r] * cv;
+    }
+    if (lane >= 6) {  // K6 = X^T D
+#pragma unroll
+      for (int k = 0; k < 6; k++) col[k] *= d[k];
     }
     if (!vec_done) {  // (iekf_update_block computes it beside the sum)
       if (lane == 63) iekf_vec(st, L);

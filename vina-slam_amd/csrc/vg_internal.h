@@ -809,6 +809,9 @@ int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, co
               double end, const double* imu, int m);
 int host_win_count(vg_ctx* ctx);
 int host_memo_probe(vg_ctx* ctx, int* out);  // map_memo_probe with the context's map parameters
+int iekf_update_test(vg_ctx* ctx, int nb, const double* partials, int n_points, const double* x_curr,
+                     const double* x_prop, int it, int rematch, double* x_out, double* G6_out,
+                     int* flags_out);  // vgx_iekf_update
 // shard.cpp
 int shard_alloc(vg_ctx* ctx);
 void shard_free(vg_ctx* ctx);

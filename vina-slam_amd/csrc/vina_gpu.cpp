@@ -1104,6 +1104,18 @@ extern "C" int vgx_ba_solve(vg_ctx* ctx, const double* A, const double* b, doubl
   return vg::ba_solve_test(ctx, A, b, x);
 }
 
+// Test-only: one k_iekf_update launch on given sums (iekf.hip iekf_update_test:
+// nb >= 0 block partials through the ordered reduction, nb < 0 the 34 final
+// sums). G6_out holds 96 doubles (G6 15 x 6, then nnt). The context must not be
+// stepped after.
+extern "C" int vgx_iekf_update(vg_ctx* ctx, int nb, const double* partials, int n_points, const double* x_curr,
+                               const double* x_prop, int it, int rematch, double* x_out, double* G6_out,
+                               int* flags_out) {
+  if (!ctx || !partials || !x_curr || !x_prop || !x_out || !G6_out || !flags_out) return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  return vg::iekf_update_test(ctx, nb, partials, n_points, x_curr, x_prop, it, rematch, x_out, G6_out, flags_out);
+}
+
 int vg_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters) {
   if (!ctx || (!xyz && n > 0) || n < 0 || !state || !valid || !iters) return VG_E_ARG;
   return host_lio_kdtree(ctx, xyz, n, state, valid, iters);

@@ -174,6 +174,11 @@ def lib():
             L.vgx_memo_probe.argtypes = [P, ip]
         if hasattr(L, "vgx_roots"):
             L.vgx_roots.argtypes = [P, ctypes.POINTER(ctypes.c_longlong), dp, ip, ip, ip, ctypes.c_int, ip]
+        if hasattr(L, "vgx_la_eval"):
+            L.vgx_la_eval.argtypes = [P, ctypes.c_int, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int]
+        if hasattr(L, "vgx_iekf_update"):
+            L.vgx_iekf_update.argtypes = [P, ctypes.c_int, dp, ctypes.c_int, dp, dp, ctypes.c_int, ctypes.c_int, dp,
+                                          dp, ip]
         _lib = L
     return _lib
 
@@ -522,6 +527,35 @@ class Context:
         x = np.zeros(b.shape[0])
         self._chk(lib().vgx_ba_solve(self.h, _d(A), _d(b), _d(x)), "vgx_ba_solve")
         return x
+
+    LA_OPS = {"eig3": (0, 9, 12), "exp": (1, 3, 9), "exp_dt": (2, 4, 9), "log": (3, 9, 3), "jr": (4, 3, 9),
+              "jr_inv": (5, 9, 9), "inverse6": (6, 36, 36), "inverse15": (7, 225, 225), "colpiv_qr": (8, 33, 3),
+              "clu_cov": (9, 10, 9), "clu_transform": (10, 22, 10)}
+
+    def la_eval(self, op, x):
+        """vg_la.h on the device, one item per row of x (vgx_la_eval, la_probe.hip): (n, in) -> (n, out)."""
+        code, nin, nout = self.LA_OPS[op]
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, nin)
+        out = np.zeros((x.shape[0], nout))
+        self._chk(lib().vgx_la_eval(self.h, code, _d(x), nin, _d(out), nout, x.shape[0]), "vgx_la_eval")
+        return out
+
+    def iekf_update(self, partials, n_points, x_curr, x_prop, it, rematch, reduce=False):
+        """One k_iekf_update launch (vgx_iekf_update) on the 34 final sums, or with
+        reduce on (nb, 34) block partials. Returns x_curr after the update (250),
+        G6 (15, 6), nnt (6) and [iters, matches[it], rematch, done]. The context
+        must not be stepped afterwards."""
+        p = np.ascontiguousarray(partials, dtype=np.float64)
+        nb = p.reshape(-1, 34).shape[0] if reduce else -1
+        assert reduce or p.size == 34
+        xc = np.ascontiguousarray(x_curr, dtype=np.float64)
+        xp = np.ascontiguousarray(x_prop, dtype=np.float64)
+        assert xc.size == STATE_LEN and xp.size == STATE_LEN
+        xo, g = np.zeros(STATE_LEN), np.zeros(96)
+        fl = np.zeros(4, dtype=np.int32)
+        self._chk(lib().vgx_iekf_update(self.h, nb, _d(p), n_points, _d(xc), _d(xp), it, rematch, _d(xo), _d(g),
+                                        fl.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "vgx_iekf_update")
+        return xo, g[:90].reshape(15, 6), g[90:], fl
 
 
 class Sync:
