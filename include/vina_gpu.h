@@ -333,8 +333,81 @@ int vg_poll_rows(vg_ctx* ctx, double* traj, int traj_from, int traj_cap, double*
  * section 3), so "every third" selects from that order. Completes outstanding
  * work; *n = points of the last window BA (0 if none ran while enabled). */
 int vg_local_map(vg_ctx* ctx, float* out_xyzi, int cap, int* n);
-/* Optional per-scan outputs: bit 0 = the /map_cmap cloud (vg_local_map). */
+/* Optional per-scan outputs: bit 0 = the /map_cmap cloud (vg_local_map),
+ * bit 1 = the /voxel_plane + /voxel_normal marker events (vg_markers; the
+ * reference's General.enable_visualization, node.cpp:99-100). While bit 1 is
+ * set the steady state's one-launch scan graph is declined, as it is for
+ * bit 0: the scan runs as the insert + recut graph, the collection kernel,
+ * the LM graphs and the margi tail. With both bits clear nothing changes: the
+ * same kernels, the same graphs, the same bits.
+ * Bit 1 keeps the reference's per-plane publication flags (plane.hpp:18-21)
+ * on the device only while it is set. Setting it starts from a blank slate:
+ * nothing counts as published and nothing is pending, so a plane that exists
+ * already appears at its next plane_update (octree.cpp:441-446); clearing it
+ * drops every flag. This differs from the reference only for a caller that
+ * enables after the first scan (the reference reads the parameter once, at
+ * start-up).
+ * In sharded mode (vg_shard_* with world > 1) a rank holds only its own
+ * tiles' roots: setting bit 1 returns VG_E_STATE. */
 int vg_set_publish(vg_ctx* ctx, int flags);
+
+/* One record of the map's plane / normal markers (OctoTree::
+ * collect_plane_markers / collect_normal_markers, octree.cpp:758-949). The two
+ * MarkerArrays are always in step, so one record serves both: the CYLINDER of
+ * /voxel_plane is (center, quat, plane_scale), the ARROW of /voxel_normal is
+ * (center -> tip, normal_scale); both carry id and rgba. Fixed layout, 248
+ * bytes, no implicit padding. For a DELETE only id, action, layer,
+ * voxel_center and flags are meaningful (the rest is zero). */
+typedef struct vg_plane_marker {
+  double voxel_center[3]; /* OctoTree::voxel_center */
+  double quater_length;   /* OctoTree::quater_length */
+  double center[3];       /* plane.center: marker.pose.position / points[0] (octree.cpp:802-804, 901-904) */
+  double normal[3];       /* plane.normal.normalized() (octree.cpp:806, 906) */
+  double quat[4];         /* x y z w: FromTwoVectors(UnitZ, normal) (octree.cpp:807-811) */
+  double plane_scale[3];  /* 3 sqrt(ev2), 3 sqrt(ev1), 2 sqrt(ev0), ev = max(0, eig_value) (octree.cpp:813-818) */
+  double tip[3];          /* center + normal * 2 quater_length: points[1] (octree.cpp:907-910) */
+  double normal_scale[3]; /* (0.1, 0.2, 0) * 2 quater_length (octree.cpp:915-917) */
+  double eig[3];          /* OctoTree::eig_value as stored (not clamped) */
+  double trace;           /* plane_var.block<3,3>(0,0).diagonal().sum() (octree.cpp:787-788) */
+  float rgba[4];          /* map_jet(pow(min(trace, 0.25) / 0.25, 0.2)) bytes / 255.0f, alpha 0.8 (octree.cpp:789-795, 820-823) */
+  int32_t id;             /* voxel_id_from_center(voxel_center, layer) (octree.cpp:11-21) */
+  int32_t action;         /* visualization_msgs::Marker: 0 = ADD, 2 = DELETE */
+  int32_t layer;
+  int32_t flags;          /* bit 0 plane.is_plane, bit 1 octo_state, bit 2 the node's root is in surf_map_slide,
+                             bit 3 is_update, bit 4 is_published (bits 3, 4: as the call found them) */
+} vg_plane_marker;
+
+/* The marker events of the last scan, collected on the device where the
+ * reference collects them (local_mapping.cpp:455-470): after the scan's
+ * multi_recut, before the window BA and multi_margi, on every steady-state
+ * scan (also while the window is filling; none during the cold-start
+ * initialisation) while vg_set_publish bit 1 is set. Per node of the
+ * surf_map_slide subtrees the rule of octree.cpp:761-850: a leaf that lost
+ * its plane, or a node that became internal, after it was published -> DELETE;
+ * a plane leaf updated since its last publication -> ADD. Order unspecified
+ * (the reference's is its unordered_map's). Every event is emitted: the
+ * reference's used_ids de-duplication of colliding ids is the caller's
+ * (vina::NodeCore does it).
+ * *n = events that scan emitted; min(*n, cap) records are copied. *deferred =
+ * events that did not fit the device buffer (vg_marker_capacity): their nodes'
+ * flags were left untouched, so they come out on a later scan. Completes
+ * outstanding work first, as vg_local_map does. */
+int vg_markers(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferred);
+/* Size of the device's event buffer, in records. Default 65536 (15.5 MiB of
+ * HBM, allocated only while bit 1 is set). Call before enabling: VG_E_STATE
+ * while bit 1 is set. */
+int vg_marker_capacity(vg_ctx* ctx, int max_records);
+/* Snapshot of the map in the same record type (action = 0): the user-facing
+ * "give me the planes". Independent of vg_set_publish; changes no flag.
+ * flags bit 0: only the subtrees of surf_map_slide's roots (default: the whole
+ * map); bit 1: every node with layer <= max_layer (default: plane leaves only;
+ * the marker fields of a node whose flags bit 0 is clear come from
+ * its last plane record, zero if it never had one). out == NULL queries the
+ * count; else min(*n, cap) records are copied, in unspecified order. Completes
+ * outstanding work; may be called between scans, and in the stage API between
+ * vg_multi_recut and vg_damping_iter / vg_multi_margi (the reference's
+ * collection point). */
+int vg_map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n);
 
 /* ---- Spatial-tile sharding (north_star: the voxel map shards by spatial tile
  * across the GPUs of one node, with an all-reduce of the normal equations).

@@ -101,6 +101,27 @@ class LioCore {
     check(vg_get_stats(ctx_, &st), "vg_get_stats");
     return st;
   }
+  // General.enable_visualization's collection (local_mapping.cpp:455-470): vg_set_publish
+  // bit 1, then per scan the /voxel_plane + /voxel_normal events; map_planes: a snapshot
+  void set_publish(int flags) { check(vg_set_publish(ctx_, flags), "vg_set_publish"); }
+  void marker_capacity(int max_records) { check(vg_marker_capacity(ctx_, max_records), "vg_marker_capacity"); }
+  std::vector<vg_plane_marker> markers(int* deferred = nullptr) {
+    int n = 0, d = 0;
+    check(vg_markers(ctx_, nullptr, 0, &n, &d), "vg_markers");
+    std::vector<vg_plane_marker> out((size_t)n);
+    if (n > 0) check(vg_markers(ctx_, out.data(), n, &n, &d), "vg_markers");
+    if (deferred) *deferred = d;
+    return out;
+  }
+  std::vector<vg_plane_marker> map_planes(bool slide_only = false, bool all_nodes = false) {
+    const int flags = (slide_only ? 1 : 0) | (all_nodes ? 2 : 0);
+    int n = 0;
+    check(vg_map_planes(ctx_, flags, nullptr, 0, &n), "vg_map_planes");
+    std::vector<vg_plane_marker> out((size_t)(n > 0 ? n : 1));
+    check(vg_map_planes(ctx_, flags, out.data(), n > 0 ? n : 1, &n), "vg_map_planes");
+    out.resize((size_t)n < out.size() ? (size_t)n : out.size());
+    return out;
+  }
   vg_ctx* raw() { return ctx_; }
 
  private:

@@ -11,6 +11,10 @@
 //   ResultOutput::pub_localmap (publishers.cpp:99-131, local_mapping.cpp:505):
 //     the path's window rows re-written with the BA-refined positions (in
 //     path()) and the /map_cmap cloud -> local_map();
+//   the /voxel_plane + /voxel_normal MarkerArrays of every steady-state scan
+//     (General.enable_visualization, node.cpp:99-100; local_mapping.cpp:455-470,
+//     OctoTree::collect_plane_markers / collect_normal_markers) ->
+//     enable_visualization() / voxel_plane() / voxel_normal();
 //   FileReaderWriter::save_pose_tum (io.cpp:67-77) -> tum_rows() / tum_line /
 //     write_tum (steady-state scans only, as the reference's file).
 // Outputs are refreshed without draining the device pipeline (vg_poll): a
@@ -23,6 +27,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <unordered_set>
 #include <vector>
 #include "vina_gpu.hpp"
 
@@ -135,6 +140,7 @@ class NodeCore {
             "vg_step_deskew");
       scans_.erase(it);
       stepped++;
+      if (visualization_) take_markers();
     }
     poll();
     return stepped;
@@ -163,7 +169,34 @@ class NodeCore {
 
   // /map_cmap (pub_localmap): switch the device-side cloud on (from the next
   // window BA on) and read the last one: x y z intensity per point
-  void enable_local_map(bool on) { check(vg_set_publish(lio_.raw(), on ? 1 : 0), "vg_set_publish"); }
+  void enable_local_map(bool on) {
+    publish_ = (publish_ & ~1) | (on ? 1 : 0);
+    check(vg_set_publish(lio_.raw(), publish_), "vg_set_publish");
+  }
+  // General.enable_visualization (node.cpp:99-100): call before the first
+  // scan, as the reference reads the parameter at start-up. While on, spin()
+  // reads every stepped scan's marker events (which completes that scan) into
+  // voxel_plane() / voxel_normal(): the two MarkerArrays the reference
+  // publishes after the scan's multi_recut (local_mapping.cpp:455-470), each
+  // holding the events of the scans stepped since clear_markers(). Within one
+  // scan's array the first record of an id wins and later records with that id
+  // are dropped — the reference's used_ids; a hash collision hides the second
+  // leaf there too, which one follows its map order there and the device's
+  // emission order here. One record serves both topics (vg_plane_marker), and
+  // the two collectors see the same flags and ids, so the two arrays are one.
+  void enable_visualization(bool on) {
+    publish_ = (publish_ & ~2) | (on ? 2 : 0);
+    check(vg_set_publish(lio_.raw(), publish_), "vg_set_publish");
+    visualization_ = on;
+  }
+  const std::vector<vg_plane_marker>& voxel_plane() const { return markers_; }
+  const std::vector<vg_plane_marker>& voxel_normal() const { return markers_; }
+  // per steady-state scan stepped since clear_markers(): its record count
+  const std::vector<int>& marker_scan_counts() const { return marker_counts_; }
+  void clear_markers() {
+    markers_.clear();
+    marker_counts_.clear();
+  }
   std::vector<float> local_map() {
     int n = 0;
     check(vg_local_map(lio_.raw(), nullptr, 0, &n), "vg_local_map");
@@ -219,6 +252,29 @@ class NodeCore {
   void check(int r, const char* what) {
     if (r != VG_OK) throw Error(r, std::string(what) + ": " + vg_last_error(lio_.raw()));
   }
+  // one steady-state scan's events -> the arrays, under the used_ids rule. The
+  // initialisation's scans publish nothing (the reference collects in the
+  // steady-state branch only), so they add no array, not even an empty one.
+  void take_markers() {
+    vg_stats st;
+    check(vg_get_stats(lio_.raw(), &st), "vg_get_stats");  // completes the scan
+    if (st.init_phase != 0) return;
+    if (marker_buf_.empty()) marker_buf_.resize(4096);
+    int n = 0, deferred = 0;
+    check(vg_markers(lio_.raw(), marker_buf_.data(), (int)marker_buf_.size(), &n, &deferred), "vg_markers");
+    if (n > (int)marker_buf_.size()) {  // grown once to the scan's size, then one call per scan
+      marker_buf_.resize((size_t)n);
+      check(vg_markers(lio_.raw(), marker_buf_.data(), n, &n, &deferred), "vg_markers");
+    }
+    std::unordered_set<int> used_ids;
+    int kept = 0;
+    for (int i = 0; i < n; i++)
+      if (used_ids.insert(marker_buf_[i].id).second) {
+        markers_.push_back(marker_buf_[i]);
+        kept++;
+      }
+    marker_counts_.push_back(kept);
+  }
   static PoseStamped row_pose(const double* r) {
     PoseStamped s;
     s.t = r[0];
@@ -253,6 +309,10 @@ class NodeCore {
   int next_id_ = 0;
   int scans_done_ = 0;
   std::vector<PoseStamped> tum_, path_;
+  int publish_ = 0;  // vg_set_publish flags
+  bool visualization_ = false;
+  std::vector<vg_plane_marker> markers_, marker_buf_;
+  std::vector<int> marker_counts_;
 };
 
 }  // namespace vina_gpu

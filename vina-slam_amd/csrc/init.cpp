@@ -763,6 +763,10 @@ int init_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, co
   P->ins_slot = -1;
   P->prefix = false;
   P->rc_seq = 0;
+  // no marker collection on this scan: the reference collects in the steady-state
+  // branch only (local_mapping.cpp:455-470), and this tail belongs to the initialisation
+  P->mk_done = true;
+  ctx->mk_fresh = false;
   if (c.if_BA == 1) VG_TRY(stage_ba(ctx, nullptr, true));
   VG_TRY(stage_margi_slide(ctx));
   return stage_finish(ctx);

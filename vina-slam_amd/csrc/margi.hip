@@ -134,7 +134,8 @@ __global__ void __launch_bounds__(256) k_margi_leaf(const int* __restrict__ nlea
                                                     const double* __restrict__ fac_eig, const Clu* __restrict__ fac_pcr,
                                                     int* __restrict__ plan, const int* __restrict__ gate,
                                                     unsigned* __restrict__ head_flag, int batch,
-                                                    const int* __restrict__ dseq, const unsigned* __restrict__ pre_flag) {
+                                                    const int* __restrict__ dseq, const unsigned* __restrict__ pre_flag,
+                                                    int mk_on) {
   if (gate && !*gate) return;  // a speculative tail the LM did not reach (ba_run)
   if (pre_flag && blockIdx.x > 0) {  // the scan graph: the leaves read the margi prefix's lists (d_sync[4] >= ph[4])
     // Normally the prefix ended long before (it runs under the LM): its
@@ -276,6 +277,7 @@ __global__ void __launch_bounds__(256) k_margi_leaf(const int* __restrict__ nlea
         if (add_.N - h.last_num >= 5 || h.last_num <= 10) {
           plane_update_dev(m, node, add_, e);
           h.last_num = add_.N;
+          if (mk_on) h.mk |= kMkUpdated;  // plane.is_update / is_normal_update (octree.cpp:441-446), markers.hip
           n_pu++;
         }
       PMG(pc);
@@ -701,7 +703,7 @@ int map_margi(vg_ctx* ctx, const MP& mp, const WinArg& wa, int n_oldest, int thr
   k_margi_leaf<<<1 + 512 * kBlock / kSpreadBlock, kSpreadBlock, 0, s>>>(
       m.counters + kCntLeaves, w.list0, mp, wa2, ctx->st, dwin, dn, dn + 32, bi != nullptr, bi,
       bi ? ba_hess_dev(ctx) : nullptr, ctx->d_pub, pub_seq, m, ctx->ba.fac_eig, ctx->ba.fac_pcr, w.plan, gate,
-      flags ? ctx->d_sync + 2 : nullptr, ctx->margi_batch ? 1 : 0, nullptr, nullptr);
+      flags ? ctx->d_sync + 2 : nullptr, ctx->margi_batch ? 1 : 0, nullptr, nullptr, (ctx->pub_flags & 2) ? 1 : 0);
   VG_HIP(hipEventRecord(ctx->ev_tail_a, s));
   // the margi's publication number into the IEKF hand-off flag: by the margi
   // graph's first kernel (k_margi_copy) — or k_sync_set when the local map
@@ -764,7 +766,7 @@ int map_margi_tail_capture(vg_ctx* ctx, const MP& mp, const WinArg& wa) {
   k_margi_leaf<<<1 + 512 * kBlock / kSpreadBlock, kSpreadBlock, 0, s>>>(
       m.counters + kCntLeaves, w.list0, mp, wa, ctx->st, dwin, dn, dn + 32, 1, ba_iters_dev(ctx), ba_hess_dev(ctx),
       ctx->d_pub, 0, m, ctx->ba.fac_eig, ctx->ba.fac_pcr, w.plan, gate, ctx->d_sync + 2, ctx->margi_batch ? 1 : 0,
-      &ctx->st->ph[1], ctx->d_sync + 4);
+      &ctx->st->ph[1], ctx->d_sync + 4, 0);  // (no scan graph while the markers are on, scan_graph_ok)
   k_margi_copy<<<256, 64 * kCopyWaves, 0, s>>>(m.counters + kCntLeaves, w.plan, dwin, m, gate, w.list0,
                                                 ctx->margi_fused ? 1 : 0, ctx->d_sync, ctx->st);
   if (ctx->margi_fused) {

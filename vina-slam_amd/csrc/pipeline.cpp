@@ -574,6 +574,8 @@ int stage_propagate(vg_ctx* ctx, const double* imu, int m, double beg, double en
   P->ins_slot = -1;
   P->prefix = false;
   P->tail_queued = false;
+  P->mk_done = false;
+  ctx->mk_fresh = false;
   return VG_OK;
 }
 
@@ -770,7 +772,16 @@ static bool scan_graph_ok(vg_ctx* ctx, const HostPipe* P) {
   return ctx->scan_graph && ctx->spec_tail && ctx->ba_graph && ctx->ba_graph2 && ctx->ba_last_iters == 2 &&
          ctx->flag_sync && !ctx->serial_kernels && ctx->overlap_iekf && ctx->want_ds_stream &&
          !(ctx->prof_on && !ctx->prof_clock) &&
-         ctx->dbg_capture != 1 && !(ctx->pub_flags & 1) && !P->lmp.active;
+         ctx->dbg_capture != 1 && !(ctx->pub_flags & 3) && !P->lmp.active;
+}
+// The scan's marker collection (local_mapping.cpp:455-470; vg_set_publish bit
+// 1): once per steady-state scan, on the main stream, where the scan's recut is
+// complete — a host-sized completion included — and ahead of the margi's leaf
+// pass, whose plane updates belong to the next scan's collection
+static int markers_collect_once(vg_ctx* ctx, HostPipe* P) {
+  if (!(ctx->pub_flags & 2) || P->mk_done) return VG_OK;
+  P->mk_done = true;
+  return markers_collect(ctx);
 }
 static int stage_insert_recut(vg_ctx* ctx) {
   HostTimer ht_(ctx, kHostInsert);
@@ -891,7 +902,7 @@ int stage_recut(vg_ctx* ctx, int* nf_out) {
   P->cur.st.n_factors = nf;
   P->n_factors = nf;
   if (nf_out) *nf_out = nf;
-  return VG_OK;
+  return markers_collect_once(ctx, P);
 }
 
 static int margi_enqueue(vg_ctx* ctx, HostPipe* P, const int* gate, int* seq1, int* seq2);
@@ -930,6 +941,7 @@ int stage_ba(vg_ctx* ctx, int* iters_out, bool margi_follows) {
       P->n_factors = __atomic_load_n(&ctx->h_pub->rc_nf, __ATOMIC_ACQUIRE);
       P->cur.st.n_factors = P->n_factors;
     }
+    VG_TRY(markers_collect_once(ctx, P));  // the recut is complete: behind the first LM iterations, ahead of any tail
     // after a scan graph whose recut completed on the device, the prefix and the
     // graph's tail meet on device flags (the host-completed recut records events)
     VG_TRY(map_margi_prefix(ctx, P->mpd, P->mp[0], P->wp_n[P->mp[0]], ctx->cfg.thread_num,
@@ -997,6 +1009,7 @@ static int margi_enqueue(vg_ctx* ctx, HostPipe* P, const int* gate, int* seq1, i
   const WinArg wa = make_winarg(P, 1);
   P->tail_wa = wa;
   VG_TRY(map_factor_finish(ctx));  // an asynchronous recut no k_ba_init followed (stage API without the LM)
+  VG_TRY(markers_collect_once(ctx, P));  // (... and no stage_ba collected behind)
   *seq1 = ++ctx->pub_seq;
   *seq2 = ++ctx->pub_seq;
   if (!P->prefix) {
@@ -1074,6 +1087,18 @@ int stage_finish(vg_ctx* ctx) {
 }
 
 int host_win_count(vg_ctx* ctx) { return hp(ctx)->win_count; }
+
+// for a read of the map (vg_map_planes): between scans everything outstanding;
+// inside a stage-level scan the main stream, which carries every map write of
+// the stages called so far
+int host_quiesce(vg_ctx* ctx) {
+  HostPipe* P = hp(ctx);
+  if (!P->in_scan) return host_sync(ctx);
+  if (P->sticky != VG_OK) return P->sticky;
+  VG_TRY(flush_deferred(ctx, P));
+  VG_HIP(stream_wait(ctx));
+  return VG_OK;
+}
 
 // The idle branch's journey release (local_mapping.cpp:317-344) after
 // host_sync: pending once jour has advanced (release_flag, :510-518); the

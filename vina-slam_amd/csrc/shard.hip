@@ -186,6 +186,10 @@ static int shard_common(vg_ctx* ctx, int rank, int world) {
     ctx->err = "vg_shard: call once, before the first scan";
     return VG_E_STATE;
   }
+  if (world > 1 && (ctx->pub_flags & 2)) {
+    ctx->err = "vg_shard: the plane / normal markers (vg_set_publish bit 1) are not available in sharded mode";
+    return VG_E_STATE;
+  }
   ctx->shard.rank = rank;
   ctx->shard.world = world;
   ctx->map.shard_rank = rank;

@@ -390,7 +390,7 @@ __device__ __forceinline__ void init_node(NodeHdr& h, const double c[3], float q
   h.isexist = 0;
   h.is_plane = 0;
   h.has_sw = 0;
-  h.pad0 = h.pad1 = h.pad2 = 0;
+  h.mk = h.pad1 = h.pad2 = 0;
   h.opt_state = -1;
   h.last_num = 0;
   h.fix_off = 0;

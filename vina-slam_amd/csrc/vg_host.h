@@ -172,6 +172,7 @@ struct HostPipe {
   bool published = false;
   bool prefix = false;     // map_margi_prefix enqueued for this scan
   bool tail_queued = false;  // the margi tail went in behind the LM and its gate opened (ba_run)
+  bool mk_done = false;      // the scan's marker collection is on the stream (markers_collect_once)
   int tail_seq1 = 0, tail_seq2 = 0;  // that tail's publication numbers
   WinArg tail_wa;                    // and its window view (before the host's slide)
   // the previous fused step's LM, not resolved yet (stage_ba, ctx->ba_loop):

@@ -118,7 +118,7 @@ struct NodeHdr {            // 96 B: everything the correspondence descent reads
   int child[8];             // leaves[8] (-1 = none)
   float qlen;               // quater_length
   int8_t layer, octo, isexist, is_plane;
-  int8_t has_sw, pad0, pad1, pad2;
+  int8_t has_sw, mk, pad1, pad2;  // mk: marker publication flags (kMkUpdated | kMkPublished, markers.hip)
   int opt_state, last_num;
   int fix_off, fix_cnt, fix_cap;
   int parent;
@@ -130,6 +130,10 @@ struct PlaneRec {           // 224 B: Plane (plane.hpp:5-24) as read by OctoTree
   int pad;
 };
 constexpr int kCovN = 45;   // cov_add packed upper 9x9
+// Plane's publication flags (plane.hpp:18-21) in NodeHdr::mk: is_update /
+// is_normal_update and is_published / is_normal_published move in lock-step
+// (the two collectors run back to back), so one pair of bits serves both
+constexpr int kMkUpdated = 1, kMkPublished = 2;
 
 struct DevMap {
   int cap_nodes = 0, cap_fix = 0, hash_mask = 0, W = 0, cap_wp = 0;
@@ -448,7 +452,12 @@ struct vg_ctx {
   bool ins_ev_pending = false;  // ev_ds_free / ev_recut_done of the last insert+recut graph not recorded yet
   bool use_graphs = true;  // margi prefix on the second stream
   bool overlap_iekf = true;  // the next IEKF under the margi remainder (lio_state_estimation)
-  int pub_flags = 0;         // vg_set_publish: bit 0 = /map_cmap after each window BA (k_local_map)
+  int pub_flags = 0;         // vg_set_publish: bit 0 = /map_cmap after each window BA (k_local_map),
+                             // bit 1 = the /voxel_plane + /voxel_normal events after each recut (markers.hip)
+  vg_plane_marker* d_mk = nullptr;  // the last collection's event records (allocated while bit 1 is set)
+  int* d_mk_cnt = nullptr;          // [0] events reserved by the last collection (past mk_cap: deferred)
+  int mk_cap = 1 << 16;             // vg_marker_capacity
+  bool mk_fresh = false;            // the last opened scan ran a collection
   float4* d_cmap = nullptr;  // the last /map_cmap cloud (x, y, z, intensity) and its size
   int* d_cmap_n = nullptr;
   bool ds_early = true;      // a fused step's downsample enqueued before the host waits for the previous state (host_step)
@@ -835,6 +844,13 @@ bool host_release_pending(vg_ctx* ctx);  // jour advanced in an absorbed scan si
 // lifetime.hip: the journey release + the node pool / point_fix arena compaction
 int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, long long* out);
 int map_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, int* nodes, int* nfix, int cap, int* count);
+// markers.hip: the /voxel_plane + /voxel_normal events (local_mapping.cpp:455-470)
+int markers_enable(vg_ctx* ctx, bool on);  // blank slate either way; the event buffer lives while on
+int markers_collect(vg_ctx* ctx);          // one collection over surf_map_slide, on the context stream
+int markers_read(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferred);
+int map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n);
+void markers_free(vg_ctx* ctx);
+int host_quiesce(vg_ctx* ctx);  // host_sync between scans; inside an open scan the context stream's drain
 int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters);
 int decode_scan(vg_ctx* ctx, const void* records, int n, const vg_lidar_format* fmt, float* xyz, float* inten,
                 float* time, int* n_out);  // decode.hip

@@ -299,6 +299,7 @@ int vg_destroy(vg_ctx* ctx) {
   if (ctx->arena.base) (void)hipFree(ctx->arena.base);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->dbg_cap_buf) (void)hipFree(ctx->dbg_cap_buf);
+  markers_free(ctx);
   shard_free(ctx);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);
@@ -359,7 +360,8 @@ int vg_reset(vg_ctx* ctx) {
   VG_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->stream_iekf) VG_HIP(hipStreamSynchronize(ctx->stream_iekf));
   ctx->ba_loop.active = false;  // the HostPipe's record of it goes with host_reset
-  VG_TRY(map_reset(ctx));
+  VG_TRY(map_reset(ctx));  // (the marker flags go with the node records: every node is allocated anew)
+  ctx->mk_fresh = false;
   // the device's jour with the host's (host_reset: 0)
   VG_HIP(hipMemset(&ctx->st->jour_check, 0, offsetof(DState, imurec) - offsetof(DState, jour_check)));
   VG_TRY(kd_reset(ctx));
@@ -668,11 +670,39 @@ int vg_path(vg_ctx* ctx, double* out, int cap, int* n) {
 }
 
 int vg_set_publish(vg_ctx* ctx, int flags) {
-  if (!ctx || (flags & ~1)) return VG_E_ARG;
+  if (!ctx || (flags & ~3)) return VG_E_ARG;
+  if ((flags & 2) && ctx->shard.world > 1) {
+    ctx->err = "vg_set_publish: the plane / normal markers are not available in sharded mode";
+    return VG_E_STATE;
+  }
   VG_TRY(host_sync(ctx));
   if ((flags & 1) && !(ctx->pub_flags & 1)) VG_HIP(hipMemset(ctx->d_cmap_n, 0, sizeof(int)));
+  // the publication flags live only while bit 1 is set: a blank slate on either edge (vina_gpu.h)
+  if ((flags ^ ctx->pub_flags) & 2) VG_TRY(markers_enable(ctx, (flags & 2) != 0));
   ctx->pub_flags = flags;
   return VG_OK;
+}
+
+int vg_markers(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferred) {
+  if (!ctx || !n || cap < 0 || (cap > 0 && !out)) return VG_E_ARG;
+  VG_TRY(host_sync(ctx));
+  return markers_read(ctx, out, cap, n, deferred);
+}
+
+int vg_marker_capacity(vg_ctx* ctx, int max_records) {
+  if (!ctx || max_records < 1 || max_records > (1 << 23)) return VG_E_ARG;
+  if (ctx->pub_flags & 2) {
+    ctx->err = "vg_marker_capacity: the markers are enabled (set the capacity before vg_set_publish bit 1)";
+    return VG_E_STATE;
+  }
+  ctx->mk_cap = max_records;
+  return VG_OK;
+}
+
+int vg_map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n) {
+  if (!ctx || !n || (flags & ~3) || cap < 0) return VG_E_ARG;
+  VG_TRY(host_quiesce(ctx));
+  return map_planes(ctx, flags, out, cap, n);
 }
 
 int vg_local_map(vg_ctx* ctx, float* out_xyzi, int cap, int* n) {

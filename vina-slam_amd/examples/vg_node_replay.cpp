@@ -22,7 +22,7 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    fprintf(stderr, "usage: %s events.bin out_tum.txt [device [out_path.txt [out_cmap.bin]]]\n", argv[0]);
+    fprintf(stderr, "usage: %s events.bin out_tum.txt [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]\n", argv[0]);
     return 2;
   }
   FILE* f = fopen(argv[1], "rb");
@@ -47,6 +47,18 @@ int main(int argc, char** argv) {
     vina_gpu::NodeCore node(cfg, &cap, fmt, point_notime, argc > 3 ? atoi(argv[3]) : 0);
     if (has_seed) node.lio().seed(seed);
     if (argc > 5) node.enable_local_map(true);  // /map_cmap after every window BA
+    // /voxel_plane + /voxel_normal (General.enable_visualization): per stepped scan an int32 record
+    // count, then that scan's vg_plane_marker records (one record serves both topics)
+    FILE* fm = nullptr;
+    size_t n_markers = 0;
+    if (argc > 6) {
+      fm = fopen(argv[6], "wb");
+      if (!fm) {
+        perror("markers");
+        return 1;
+      }
+      node.enable_visualization(true);
+    }
     std::vector<unsigned char> rec;
     int n_imu = 0, n_msg = 0, n_step = 0;
     for (;;) {
@@ -67,7 +79,22 @@ int main(int argc, char** argv) {
         n_msg++;
       }
       n_step += node.spin();
+      if (fm) {
+        size_t at = 0;
+        for (const int cnt : node.marker_scan_counts()) {
+          const int32_t c = cnt;
+          if (fwrite(&c, sizeof(c), 1, fm) != 1 ||
+              fwrite(node.voxel_plane().data() + at, sizeof(vg_plane_marker), (size_t)cnt, fm) != (size_t)cnt) {
+            perror("markers");
+            return 1;
+          }
+          at += (size_t)cnt;
+        }
+        n_markers += at;
+        node.clear_markers();
+      }
     }
+    if (fm) fclose(fm);
     const std::vector<float> w = node.scan_world();
     if (!node.write_tum(argv[2])) {
       perror("tum");
@@ -95,8 +122,8 @@ int main(int argc, char** argv) {
       fclose(fc);
     }
     printf("{\"imu\": %d, \"scans\": %d, \"stepped\": %d, \"poses\": %zu, \"path\": %zu, "
-           "\"last_scan_world_points\": %zu, \"cmap_points\": %zu}\n",
-           n_imu, n_msg, n_step, node.tum_rows().size(), node.path().size(), w.size() / 3, ncmap);
+           "\"last_scan_world_points\": %zu, \"cmap_points\": %zu, \"marker_records\": %zu}\n",
+           n_imu, n_msg, n_step, node.tum_rows().size(), node.path().size(), w.size() / 3, ncmap, n_markers);
   } catch (const vina_gpu::Error& e) {
     fprintf(stderr, "vg_node_replay: %s (code %d)\n", e.what(), e.code);
     return 1;

@@ -14,7 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CONFIG_DIR = os.path.join(os.path.dirname(HERE), "configs")
 
 DEFAULTS = {
-    "General": {"blind": 0.1, "extrinsic_tran": [0.0] * 3, "extrinsic_rota": [1, 0, 0, 0, 1, 0, 0, 0, 1], "if_BA": 0},
+    "General": {"blind": 0.1, "extrinsic_tran": [0.0] * 3, "extrinsic_rota": [1, 0, 0, 0, 1, 0, 0, 0, 1], "if_BA": 0,
+                # node.cpp:99-100; not part of the C config: a caller acts on it with Context.set_publish(2)
+                "enable_visualization": 0},
     "Odometry": {"cov_gyr": 0.1, "cov_acc": 0.1, "rdw_gyr": 1e-4, "rdw_acc": 1e-4, "down_size": 0.1,
                  "dept_err": 0.02, "beam_err": 0.05, "voxel_size": 1.0, "min_eigen_value": 0.0025},
     "LocalBA": {"win_size": 10, "max_layer": 2, "cov_gyr": 0.1, "cov_acc": 0.1, "rdw_gyr": 1e-4, "rdw_acc": 1e-4,

@@ -51,6 +51,24 @@ class Stats(ctypes.Structure):
                 ("init_valid", ctypes.c_int), ("iekf_points", ctypes.c_int)]
 
 
+class VgPlaneMarker(ctypes.Structure):
+    """vg_plane_marker (include/vina_gpu.h): one record of the /voxel_plane + /voxel_normal markers."""
+    _fields_ = [("voxel_center", ctypes.c_double * 3), ("quater_length", ctypes.c_double),
+                ("center", ctypes.c_double * 3), ("normal", ctypes.c_double * 3), ("quat", ctypes.c_double * 4),
+                ("plane_scale", ctypes.c_double * 3), ("tip", ctypes.c_double * 3),
+                ("normal_scale", ctypes.c_double * 3), ("eig", ctypes.c_double * 3), ("trace", ctypes.c_double),
+                ("rgba", ctypes.c_float * 4), ("id", ctypes.c_int32), ("action", ctypes.c_int32),
+                ("layer", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+# the same layout as a numpy record type (what the marker calls return)
+MARKER_DTYPE = np.dtype([("voxel_center", "<f8", 3), ("quater_length", "<f8"), ("center", "<f8", 3),
+                         ("normal", "<f8", 3), ("quat", "<f8", 4), ("plane_scale", "<f8", 3), ("tip", "<f8", 3),
+                         ("normal_scale", "<f8", 3), ("eig", "<f8", 3), ("trace", "<f8"), ("rgba", "<f4", 4),
+                         ("id", "<i4"), ("action", "<i4"), ("layer", "<i4"), ("flags", "<i4")])
+MARKER_EVAL_IN = 15  # vgx_marker_eval: voxel_center 3, layer, quater_length, center 3, normal 3, trace, eig 3
+
+
 def _stats_dict(s):
     return {k: (list(getattr(s, k)) if k in ("iekf_matches", "iekf_planes") else getattr(s, k))
             for k, _ in Stats._fields_}
@@ -139,6 +157,14 @@ def lib():
         L.vg_poll_rows.argtypes = [P, dp, ctypes.c_int, ctypes.c_int, dp, ctypes.c_int]
         L.vg_local_map.argtypes = [P, fp, ctypes.c_int, ip]
         L.vg_set_publish.argtypes = [P, ctypes.c_int]
+        L.has_markers = hasattr(L, "vg_markers")  # a build older than the markers (A/B runs): _need_markers says so
+        if L.has_markers:
+            mp = ctypes.POINTER(VgPlaneMarker)
+            L.vg_markers.argtypes = [P, mp, ctypes.c_int, ip, ip]
+            L.vg_marker_capacity.argtypes = [P, ctypes.c_int]
+            L.vg_map_planes.argtypes = [P, ctypes.c_int, mp, ctypes.c_int, ip]
+            L.vgx_marker_eval.argtypes = [P, dp, ctypes.c_int, mp]
+            L.vgx_marker_sizeof.argtypes = []
         L.vg_scan_load.argtypes = [P, fp, fp, ctypes.c_int]
         L.vg_scan_bind_dev.argtypes = [P, P, P, P, P, ctypes.c_int]
         L.vg_propagate.argtypes = [P, dp, ctypes.c_int, ctypes.c_double, ctypes.c_double]
@@ -252,6 +278,10 @@ class Context:
         self._chk(lib().vg_downsample_close(self.h, _f(xyz), None if t is None else _f(t), xyz.shape[0], size,
                                             _f(out), ctypes.byref(n)), "vg_downsample_close")
         return out[: n.value]
+
+    def reset(self):
+        """Drop the map and the window (vg_reset, the reference's system_reset)."""
+        self._chk(lib().vg_reset(self.h), "vg_reset")
 
     def seed(self, state):
         s = np.ascontiguousarray(state, dtype=np.float64)
@@ -383,6 +413,47 @@ class Context:
 
     def set_publish(self, flags):
         self._chk(lib().vg_set_publish(self.h, flags), "vg_set_publish")
+
+    def _need_markers(self):
+        if not lib().has_markers:
+            raise VgError("%s has no marker entry points (vg_markers, vg_map_planes): rebuild it" % LIB)
+
+    def marker_capacity(self, max_records):
+        """Size of the device's marker event buffer (vg_marker_capacity); before set_publish(2)."""
+        self._need_markers()
+        self._chk(lib().vg_marker_capacity(self.h, max_records), "vg_marker_capacity")
+
+    def markers(self):
+        """The last scan's /voxel_plane + /voxel_normal events (vg_markers): (records as a MARKER_DTYPE
+        array, events deferred to a later scan because the device buffer was full)."""
+        self._need_markers()
+        n, d = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(lib().vg_markers(self.h, None, 0, ctypes.byref(n), ctypes.byref(d)), "vg_markers")
+        out = np.zeros(max(n.value, 1), dtype=MARKER_DTYPE)
+        self._chk(lib().vg_markers(self.h, out.ctypes.data_as(ctypes.POINTER(VgPlaneMarker)), n.value,
+                                   ctypes.byref(n), ctypes.byref(d)), "vg_markers")
+        return out[: n.value], d.value
+
+    def map_planes(self, slide_only=False, all_nodes=False):
+        """Snapshot of the map's planes (vg_map_planes) as a MARKER_DTYPE array: plane leaves, or with
+        all_nodes every node down to max_layer; slide_only: under surf_map_slide's roots only."""
+        self._need_markers()
+        flags = (1 if slide_only else 0) | (2 if all_nodes else 0)
+        n = ctypes.c_int(0)
+        self._chk(lib().vg_map_planes(self.h, flags, None, 0, ctypes.byref(n)), "vg_map_planes")
+        out = np.zeros(max(n.value, 1), dtype=MARKER_DTYPE)
+        self._chk(lib().vg_map_planes(self.h, flags, out.ctypes.data_as(ctypes.POINTER(VgPlaneMarker)), n.value,
+                                      ctypes.byref(n)), "vg_map_planes")
+        return out[: n.value]
+
+    def marker_eval(self, inputs):
+        """Test hook (vgx_marker_eval): the device's marker math on (n, 15) inputs -> n records."""
+        self._need_markers()
+        a = np.ascontiguousarray(inputs, dtype=np.float64).reshape(-1, MARKER_EVAL_IN)
+        out = np.zeros(a.shape[0], dtype=MARKER_DTYPE)
+        self._chk(lib().vgx_marker_eval(self.h, _d(a), a.shape[0], out.ctypes.data_as(ctypes.POINTER(VgPlaneMarker))),
+                  "vgx_marker_eval")
+        return out
 
     def local_map(self):
         """/map_cmap of the last window BA (vg_local_map): (n, 4) float32 x, y, z, intensity."""

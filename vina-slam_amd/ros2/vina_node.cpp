@@ -10,6 +10,7 @@
 #include <sensor_msgs/msg/point_cloud2.hpp>
 #include <sensor_msgs/point_cloud2_iterator.hpp>
 #include <tf2_ros/transform_broadcaster.h>
+#include <visualization_msgs/msg/marker_array.hpp>
 #ifdef VG_HAVE_LIVOX
 #include <livox_ros_driver2/msg/custom_msg.hpp>
 #endif
@@ -60,6 +61,7 @@ class VinaNode : public rclcpp::Node {
     pose_file_ = declare_parameter("General.pose_save_path", std::string("")) +
                  declare_parameter("General.pose_filename", std::string("trajectory.txt"));
     c.if_BA = (int)declare_parameter("General.if_BA", 0);
+    const int enable_visualization = (int)declare_parameter("General.enable_visualization", 0);  // node.cpp:99-100
     c.odo_cov_gyr = declare_parameter("Odometry.cov_gyr", 0.1);
     c.odo_cov_acc = declare_parameter("Odometry.cov_acc", 0.1);
     c.odo_rdw_gyr = declare_parameter("Odometry.rdw_gyr", 1e-4);
@@ -97,6 +99,7 @@ class VinaNode : public rclcpp::Node {
     fmt_.omega_l = 3610.0;
     vg_capacity cap = {0, 0, 0, 0};
     core_ = std::make_unique<vina_gpu::NodeCore>(c, &cap, fmt_, point_notime);
+    if (enable_visualization) core_->enable_visualization(true);  // before the first scan
 
     rclcpp::QoS imu_qos(8000);
     imu_qos.keep_last(8000).best_effort();
@@ -115,6 +118,8 @@ class VinaNode : public rclcpp::Node {
     pub_scan_ = create_publisher<sensor_msgs::msg::PointCloud2>("/map_scan", 100);
     pub_path_ = create_publisher<sensor_msgs::msg::PointCloud2>("/map_path", 100);
     pub_cmap_ = create_publisher<sensor_msgs::msg::PointCloud2>("/map_cmap", 100);  // publishers.cpp:130
+    pub_voxel_plane_ = create_publisher<visualization_msgs::msg::MarkerArray>("/voxel_plane", 100);
+    pub_voxel_normal_ = create_publisher<visualization_msgs::msg::MarkerArray>("/voxel_normal", 100);
     tf_ = std::make_unique<tf2_ros::TransformBroadcaster>(*this);
   }
 
@@ -204,6 +209,7 @@ class VinaNode : public rclcpp::Node {
       publish_xyz(pub_path_, path_xyz_);
     }
     if (stepped > 0 && pub_scan_->get_subscription_count() > 0) publish_xyz(pub_scan_, core_->scan_world());
+    publish_markers();
     const bool want_cmap = pub_cmap_->get_subscription_count() > 0;
     if (want_cmap != cmap_on_) {
       core_->enable_local_map(want_cmap);
@@ -217,6 +223,77 @@ class VinaNode : public rclcpp::Node {
         for (int k = 0; k < 3; k++) xyz.push_back(c[4 * i + k]);
       publish_xyz(pub_cmap_, xyz);
     }
+  }
+
+  // /voxel_plane + /voxel_normal (local_mapping.cpp:455-470): one pair of
+  // MarkerArrays per stepped scan, from NodeCore's records (the marker fields
+  // of octree.cpp:772-848 and 872-947; a DELETE carries header, ns, id, action)
+  void publish_markers() {
+    const std::vector<int>& counts = core_->marker_scan_counts();
+    if (counts.empty()) return;
+    const std::vector<vg_plane_marker>& planes = core_->voxel_plane();
+    const std::vector<vg_plane_marker>& normals = core_->voxel_normal();
+    size_t at = 0;
+    for (const int cnt : counts) {
+      visualization_msgs::msg::MarkerArray vp, vn;
+      for (size_t i = at; i < at + (size_t)cnt; i++) {
+        vp.markers.push_back(plane_marker(planes[i]));
+        vn.markers.push_back(normal_marker(normals[i]));
+      }
+      at += (size_t)cnt;
+      pub_voxel_plane_->publish(vp);
+      pub_voxel_normal_->publish(vn);
+    }
+    core_->clear_markers();
+  }
+  static visualization_msgs::msg::Marker marker_head(const vg_plane_marker& r, const char* ns, int type) {
+    visualization_msgs::msg::Marker m;
+    m.header.frame_id = "camera_init";
+    m.ns = ns;
+    m.id = r.id;
+    if (r.action != 0) {
+      m.action = visualization_msgs::msg::Marker::DELETE;
+      return m;
+    }
+    m.type = type;
+    m.action = visualization_msgs::msg::Marker::ADD;
+    m.color.r = r.rgba[0];
+    m.color.g = r.rgba[1];
+    m.color.b = r.rgba[2];
+    m.color.a = r.rgba[3];
+    return m;
+  }
+  static visualization_msgs::msg::Marker plane_marker(const vg_plane_marker& r) {
+    visualization_msgs::msg::Marker m = marker_head(r, "plane", visualization_msgs::msg::Marker::CYLINDER);
+    if (r.action != 0) return m;
+    m.pose.position.x = r.center[0];
+    m.pose.position.y = r.center[1];
+    m.pose.position.z = r.center[2];
+    m.pose.orientation.x = r.quat[0];
+    m.pose.orientation.y = r.quat[1];
+    m.pose.orientation.z = r.quat[2];
+    m.pose.orientation.w = r.quat[3];
+    m.scale.x = r.plane_scale[0];
+    m.scale.y = r.plane_scale[1];
+    m.scale.z = r.plane_scale[2];
+    return m;
+  }
+  static visualization_msgs::msg::Marker normal_marker(const vg_plane_marker& r) {
+    visualization_msgs::msg::Marker m = marker_head(r, "normal", visualization_msgs::msg::Marker::ARROW);
+    if (r.action != 0) return m;
+    geometry_msgs::msg::Point p0, p1;
+    p0.x = r.center[0];
+    p0.y = r.center[1];
+    p0.z = r.center[2];
+    p1.x = r.tip[0];
+    p1.y = r.tip[1];
+    p1.z = r.tip[2];
+    m.points.push_back(p0);
+    m.points.push_back(p1);
+    m.scale.x = r.normal_scale[0];
+    m.scale.y = r.normal_scale[1];
+    m.scale.z = r.normal_scale[2];
+    return m;
   }
 
   void publish_xyz(const rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr& pub,
@@ -249,6 +326,7 @@ class VinaNode : public rclcpp::Node {
   rclcpp::Subscription<livox_ros_driver2::msg::CustomMsg>::SharedPtr sub_livox_;
 #endif
   rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pub_scan_, pub_path_, pub_cmap_;
+  rclcpp::Publisher<visualization_msgs::msg::MarkerArray>::SharedPtr pub_voxel_plane_, pub_voxel_normal_;
   std::vector<float> path_xyz_;
   bool cmap_on_ = false;
 };
