@@ -267,6 +267,32 @@ int vg_stats_log(vg_ctx* ctx, vg_stats* out, int cap, int* n);
  * A root still in surf_map_slide is never erased (the reference would keep a
  * dangling pointer in it; unreachable at 700 m). */
 int vg_release_far(vg_ctx* ctx, int flags, long long* out);
+/* Checkpoint and resume: everything of a context that outlives a scan — the
+ * voxel map (node records, point_fix arena, window points, slide list, the
+ * root keys), the estimator state and the host mirror with the trajectory and
+ * path rows — to one file and back. A context that loads a file and goes on
+ * stepping produces the same bits as the one that wrote it would have.
+ * vg_checkpoint_save completes the outstanding work, then compacts the node
+ * pool and the point_fix arena (as vg_release_far with flags bit 0 does:
+ * results are unchanged), so the file is proportional to the live map and
+ * independent of max_nodes / max_fix_points / hash_log2; *bytes (may be NULL)
+ * = the file's size. Between scans and in the steady state only: VG_E_STATE
+ * while a cold start is still initialising (before init_phase 3), on a sharded
+ * context (world > 1) and while a stage-level scan is open. Saving changes no
+ * later result of the saving context.
+ * vg_checkpoint_load installs a file into an existing context, fresh or used
+ * (vg_reset semantics first). The context's vg_config must equal the saved
+ * one byte for byte and max_points_per_scan must be the saver's (the window
+ * arrays' stride), else VG_E_ARG; the other capacities may differ, and a
+ * context too small returns VG_E_CAPACITY. Every check — magic and version,
+ * configuration, section table and file length, every section's checksum
+ * (recomputed on the device), capacity — runs before anything is touched: a
+ * rejected load leaves the context exactly as it was, and vg_last_error names
+ * the failed check. Not part of a checkpoint, kept as the loading context has
+ * them: vg_set_publish flags and marker state (a blank slate), the wait
+ * policy, vg_profile; vg_stats_log restarts at the load. */
+int vg_checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes);
+int vg_checkpoint_load(vg_ctx* ctx, const char* path);
 /* Window states x_buf (win_count x 250 doubles); returns win_count via *n. */
 int vg_window_states(vg_ctx* ctx, double* out, int* n);
 

@@ -104,6 +104,13 @@ class LioCore {
   // General.enable_visualization's collection (local_mapping.cpp:455-470): vg_set_publish
   // bit 1, then per scan the /voxel_plane + /voxel_normal events; map_planes: a snapshot
   void set_publish(int flags) { check(vg_set_publish(ctx_, flags), "vg_set_publish"); }
+  // checkpoint and resume (vg_checkpoint_save / vg_checkpoint_load): returns the file's bytes
+  long long save_checkpoint(const std::string& file) {
+    long long bytes = 0;
+    check(vg_checkpoint_save(ctx_, file.c_str(), &bytes), "vg_checkpoint_save");
+    return bytes;
+  }
+  void load_checkpoint(const std::string& file) { check(vg_checkpoint_load(ctx_, file.c_str()), "vg_checkpoint_load"); }
   void marker_capacity(int max_records) { check(vg_marker_capacity(ctx_, max_records), "vg_marker_capacity"); }
   std::vector<vg_plane_marker> markers(int* deferred = nullptr) {
     int n = 0, d = 0;

@@ -134,6 +134,12 @@ class NodeCore {
         continue;
       }
       if (it == scans_.end()) throw Error(VG_E_STATE, "sync_packages returned an unknown scan");
+      packages_++;
+      if (skip_ > 0) {  // resumed from a checkpoint: this package was consumed before the save
+        skip_--;
+        scans_.erase(it);
+        continue;
+      }
       Scan& sc = it->second;
       check(vg_step_deskew(lio_.raw(), sc.xyz.data(), sc.inten.data(), sc.time.data(), (int)sc.inten.size(), beg,
                            end, imu.data(), m),
@@ -141,6 +147,7 @@ class NodeCore {
       scans_.erase(it);
       stepped++;
       if (visualization_) take_markers();
+      if (package_limit_ >= 0 && packages_ >= package_limit_) break;  // (the caller saves here, then spins on)
     }
     poll();
     return stepped;
@@ -159,6 +166,29 @@ class NodeCore {
     check(vg_trajectory(lio_.raw(), nullptr, 0, &nt), "vg_trajectory");  // completes outstanding work
     poll();
   }
+
+  // Checkpoint and resume (vg_checkpoint_save / vg_checkpoint_load). Saving
+  // completes the scans in flight first. Loading replaces the context's state
+  // and then re-reads path() and tum_rows() from it — the TUM output continues
+  // the saved rows — and empties the marker arrays (the per-scan used_ids rule
+  // needs nothing older). The synchroniser's queues are not part of a
+  // checkpoint: a caller replaying a log feeds it from the start and has the
+  // first `skip_packages` packages dropped unstepped (vg_node_replay --resume).
+  long long save_checkpoint(const std::string& file) {
+    finish();
+    return lio_.save_checkpoint(file);
+  }
+  void load_checkpoint(const std::string& file) {
+    lio_.load_checkpoint(file);
+    tum_.clear();
+    path_.clear();
+    clear_markers();
+    scans_done_ = -1;  // (take_rows: read everything again)
+    finish();
+  }
+  void skip_packages(int n) { skip_ = n; }
+  void set_package_limit(int n) { package_limit_ = n; }  // spin() returns once this many packages were taken (-1: no limit)
+  int packages() const { return packages_; }             // packages sync_packages has delivered, skipped ones included
 
   // save_pose_tum's rows: the pose after the IEKF of every steady-state scan
   const std::vector<PoseStamped>& tum_rows() const { return tum_; }
@@ -308,6 +338,7 @@ class NodeCore {
   std::map<int, Scan> scans_;
   int next_id_ = 0;
   int scans_done_ = 0;
+  int packages_ = 0, skip_ = 0, package_limit_ = -1;
   std::vector<PoseStamped> tum_, path_;
   int publish_ = 0;  // vg_set_publish flags
   bool visualization_ = false;

@@ -61,6 +61,7 @@ void init_destroy(InitState* I) {
   delete I;
 }
 bool init_active(const HostPipe* P) { return P->init && P->init->active; }
+void init_finish(InitState* I) { I->active = false; }  // a loaded checkpoint is past its cold start
 
 static int init_dev(vg_ctx* ctx, InitState& I) {
   if (I.pool) return VG_OK;

@@ -236,6 +236,39 @@ int with_scratch(vg_ctx* ctx, size_t bytes, void** p, F&& body) {
 }
 }  // namespace
 
+// The root hash from (key, id) pairs filed by id (rkey[q], pos[q] = the key's
+// home slot; pos[q] = -1 for every id that is no root): clears the table and
+// runs the bidding rounds above. rcnt: 8 device ints of scratch. Shared by the
+// compaction and the checkpoint load (checkpoint.hip).
+int map_hash_place(vg_ctx* ctx, int nl, long nroots, const uint64_t* rkey, int* pos, int* rcnt, const char* who) {
+  DevMap& m = ctx->map;
+  hipStream_t s = ctx->stream;
+  const size_t hs = (size_t)m.hash_mask + 1;
+  VG_HIP(hipMemsetAsync(m.hkey, 0xff, hs * sizeof(uint64_t), s));
+  VG_HIP(hipMemsetAsync(m.hval, 0xff, hs * sizeof(int), s));
+  VG_HIP(hipMemsetAsync(m.hfirst, 0x7f, hs * sizeof(int), s));
+  int herr_h = nroots > (long)m.hash_mask ? 1 : 0;
+  constexpr int kRounds = 8;
+  for (long done = 0; !herr_h && nl > 0;) {
+    VG_HIP(hipMemsetAsync(rcnt, 0, kRounds * sizeof(int), s));
+    for (int t = 0; t < kRounds; t++) {
+      k_rel_hash_round<<<grid_for(nl), kBlock, 0, s>>>(m, nl, rkey, pos, 0, rcnt + t);
+      k_rel_hash_round<<<grid_for(nl), kBlock, 0, s>>>(m, nl, rkey, pos, 1, rcnt + t);
+    }
+    int left = 0;
+    VG_HIP(hipMemcpyAsync(&left, rcnt + kRounds - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    VG_HIP(hipStreamSynchronize(s));
+    if (left == 0) break;
+    done += kRounds;
+    if (done > (long)m.hash_mask + 1) herr_h = 1;  // (never: each round places the lowest bidder)
+  }
+  if (herr_h) {
+    ctx->err = std::string(who) + ": root hash rebuild failed";
+    return VG_E_STATE;
+  }
+  return VG_OK;
+}
+
 int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, long long* out) {
   DevMap& m = ctx->map;
   hipStream_t s = ctx->stream;
@@ -306,30 +339,8 @@ int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, lo
       const int gh = grid_for((long)m.hash_mask + 1);
       VG_HIP(hipMemsetAsync(pos, 0xff, (size_t)n_live * sizeof(int), s));
       k_rel_hash_collect<<<gh, kBlock, 0, s>>>(m, n, live, nid, rkey, pos);
-      const size_t hs = (size_t)m.hash_mask + 1;
-      VG_HIP(hipMemsetAsync(m.hkey, 0xff, hs * sizeof(uint64_t), s));
-      VG_HIP(hipMemsetAsync(m.hval, 0xff, hs * sizeof(int), s));
-      VG_HIP(hipMemsetAsync(m.hfirst, 0x7f, hs * sizeof(int), s));
       int* rcnt = (int*)(cnt + 16);  // the rounds' unplaced counts (in the scratch's 256-byte counter block)
-      int herr_h = hcnt[kRelRootsLive] > (unsigned long long)m.hash_mask ? 1 : 0;
-      constexpr int kRounds = 8;
-      for (long done = 0; !herr_h && n_live > 0;) {
-        VG_HIP(hipMemsetAsync(rcnt, 0, kRounds * sizeof(int), s));
-        for (int t = 0; t < kRounds; t++) {
-          k_rel_hash_round<<<grid_for(n_live), kBlock, 0, s>>>(m, n_live, rkey, pos, 0, rcnt + t);
-          k_rel_hash_round<<<grid_for(n_live), kBlock, 0, s>>>(m, n_live, rkey, pos, 1, rcnt + t);
-        }
-        int left = 0;
-        VG_HIP(hipMemcpyAsync(&left, rcnt + kRounds - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-        VG_HIP(hipStreamSynchronize(s));
-        if (left == 0) break;
-        done += kRounds;
-        if (done > (long)m.hash_mask + 1) herr_h = 1;  // (never: each round places the lowest bidder)
-      }
-      if (herr_h) {
-        ctx->err = "vg_release_far: root hash rebuild failed";
-        return VG_E_STATE;
-      }
+      VG_TRY(map_hash_place(ctx, n_live, (long)hcnt[kRelRootsLive], rkey, pos, rcnt, "vg_release_far"));
       // the point_fix arena: the kept blocks packed in node order (read with
       // the old records' offsets, so before the records are rewritten)
       const int gn = grid_for((long)n * 64);

@@ -293,7 +293,10 @@ int markers_enable(vg_ctx* ctx, bool on) {
   }
   int n = 0;
   VG_TRY(used_nodes(ctx, &n));
-  if (n > 0) k_mk_clear<<<grid_for(n), kBlock, 0, ctx->stream>>>(ctx->map, n);
+  // straight after a checkpoint load the flags are the saver's: enabling continues its event stream
+  const bool keep = on && ctx->mk_keep;
+  ctx->mk_keep = false;
+  if (n > 0 && !keep) k_mk_clear<<<grid_for(n), kBlock, 0, ctx->stream>>>(ctx->map, n);
   VG_HIP(hipGetLastError());
   VG_HIP(hipStreamSynchronize(ctx->stream));
   markers_free(ctx);

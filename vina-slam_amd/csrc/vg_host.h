@@ -225,6 +225,7 @@ int kd_lio(vg_ctx* ctx, int n, HX& x_curr, int* valid, int* iters);  // on the s
 InitState* init_create(vg_ctx* ctx);
 void init_destroy(InitState* I);
 bool init_active(const HostPipe* P);
+void init_finish(InitState* I);
 int init_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, const float* dt, int n,
               double beg, double end, const double* imu, int m);
 

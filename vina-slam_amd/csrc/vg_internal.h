@@ -458,6 +458,7 @@ struct vg_ctx {
   int* d_mk_cnt = nullptr;          // [0] events reserved by the last collection (past mk_cap: deferred)
   int mk_cap = 1 << 16;             // vg_marker_capacity
   bool mk_fresh = false;            // the last opened scan ran a collection
+  bool mk_keep = false;             // a checkpoint load brought the nodes' publication flags: the next enable keeps them
   float4* d_cmap = nullptr;  // the last /map_cmap cloud (x, y, z, intensity) and its size
   int* d_cmap_n = nullptr;
   bool ds_early = true;      // a fused step's downsample enqueued before the host waits for the previous state (host_step)
@@ -844,6 +845,19 @@ bool host_release_pending(vg_ctx* ctx);  // jour advanced in an absorbed scan si
 // lifetime.hip: the journey release + the node pool / point_fix arena compaction
 int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, long long* out);
 int map_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, int* nodes, int* nfix, int cap, int* count);
+// the root hash rebuilt from (key, id) pairs filed by id, by the bidding rounds (lifetime.hip)
+int map_hash_place(vg_ctx* ctx, int nl, long nroots, const uint64_t* rkey, int* pos, int* rcnt, const char* who);
+// checkpoint.hip / pipeline.cpp: the host mirror's part of a checkpoint (a byte
+// blob, one section of the file). host_ckpt_parse only reads: it fills an
+// opaque snapshot that host_ckpt_install puts in place after the reset
+// (host_ckpt_drop frees one that was not installed)
+int host_ckpt_allowed(vg_ctx* ctx, const char* who, bool save);  // VG_E_STATE: open scan, sharded, (save) cold start initialising
+void host_ckpt_blob(vg_ctx* ctx, std::vector<unsigned char>& out);
+int host_ckpt_parse(vg_ctx* ctx, const unsigned char* p, size_t n, void** snap);
+void host_ckpt_install(vg_ctx* ctx, void* snap);
+void host_ckpt_drop(void* snap);
+int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_ms);  // t_ms: 4 phase times or null
+int checkpoint_load(vg_ctx* ctx, const char* path, double* t_ms);
 // markers.hip: the /voxel_plane + /voxel_normal events (local_mapping.cpp:455-470)
 int markers_enable(vg_ctx* ctx, bool on);  // blank slate either way; the event buffer lives while on
 int markers_collect(vg_ctx* ctx);          // one collection over surf_map_slide, on the context stream

@@ -362,6 +362,7 @@ int vg_reset(vg_ctx* ctx) {
   ctx->ba_loop.active = false;  // the HostPipe's record of it goes with host_reset
   VG_TRY(map_reset(ctx));  // (the marker flags go with the node records: every node is allocated anew)
   ctx->mk_fresh = false;
+  ctx->mk_keep = false;
   // the device's jour with the host's (host_reset: 0)
   VG_HIP(hipMemset(&ctx->st->jour_check, 0, offsetof(DState, imurec) - offsetof(DState, jour_check)));
   VG_TRY(kd_reset(ctx));
@@ -632,6 +633,16 @@ int vg_release_far(vg_ctx* ctx, int flags, long long* out) {
   }
   VG_TRY(host_sync(ctx));
   return host_release_far(ctx, flags, out);
+}
+
+int vg_checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes) {
+  if (!ctx || !path) return VG_E_ARG;
+  return checkpoint_save(ctx, path, bytes, nullptr);
+}
+
+int vg_checkpoint_load(vg_ctx* ctx, const char* path) {
+  if (!ctx || !path) return VG_E_ARG;
+  return checkpoint_load(ctx, path, nullptr);
 }
 
 int vg_get_stats(vg_ctx* ctx, vg_stats* out) {
@@ -1055,6 +1066,12 @@ extern "C" int vgx_debug(vg_ctx* ctx, int key, int value) {
 // Test-only: the IEKF memo against fresh descents at internal nodes' centre
 // planes (iekf.hip k_memo_probe); out[4]: samples, mismatches of the inclusive
 // box, mismatches of the descent region k_iekf uses, samples split by the plane
+// scripts/probe_checkpoint.py: a save (load = 0) or a load with its phase times (checkpoint.hip), ms[4]
+extern "C" int vgx_checkpoint_timed(vg_ctx* ctx, const char* path, int load, long long* bytes, double* ms) {
+  if (!ctx || !path || !ms) return VG_E_ARG;
+  return load ? checkpoint_load(ctx, path, ms) : checkpoint_save(ctx, path, bytes, ms);
+}
+
 extern "C" int vgx_memo_probe(vg_ctx* ctx, int* out) {
   if (!ctx || !out) return VG_E_ARG;
   VG_TRY(host_sync(ctx));

@@ -12,16 +12,34 @@
 //                1: double header_time, int32 n, int32 stride, n*stride record bytes;
 //                -1 or end of file: done
 //
-// usage: vg_node_replay <events.bin> <out_tum.txt> [device]
+// usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
+//        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
+// --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
+// been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
+// the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "../../include/vina_node_core.hpp"
 
 static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
-int main(int argc, char** argv) {
-  if (argc < 3) {
+int main(int argc0, char** argv0) {
+  std::vector<char*> pos;
+  std::string ck_out, resume;
+  int ck_at = -1;
+  for (int i = 0; i < argc0; i++) {
+    const std::string a = argv0[i];
+    if (i + 1 < argc0 && a == "--checkpoint-out") ck_out = argv0[++i];
+    else if (i + 1 < argc0 && a == "--checkpoint-at") ck_at = atoi(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--resume") resume = argv0[++i];
+    else pos.push_back(argv0[i]);
+  }
+  const int argc = (int)pos.size();
+  char** argv = pos.data();
+  if (argc < 3 || (ck_out.empty() != (ck_at < 0))) {
     fprintf(stderr, "usage: %s events.bin out_tum.txt [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]\n", argv[0]);
     return 2;
   }
@@ -59,6 +77,18 @@ int main(int argc, char** argv) {
       }
       node.enable_visualization(true);
     }
+    if (!resume.empty()) {
+      int consumed = -1;
+      FILE* fmeta = fopen((resume + ".meta").c_str(), "r");
+      if (!fmeta || fscanf(fmeta, "%d", &consumed) != 1 || consumed < 0) {
+        fprintf(stderr, "vg_node_replay: cannot read %s.meta\n", resume.c_str());
+        return 1;
+      }
+      fclose(fmeta);
+      node.load_checkpoint(resume);
+      node.skip_packages(consumed);
+    }
+    if (ck_at >= 0) node.set_package_limit(ck_at);
     std::vector<unsigned char> rec;
     int n_imu = 0, n_msg = 0, n_step = 0;
     for (;;) {
@@ -79,6 +109,18 @@ int main(int argc, char** argv) {
         n_msg++;
       }
       n_step += node.spin();
+      if (ck_at >= 0 && node.packages() >= ck_at) {
+        const long long bytes = node.save_checkpoint(ck_out);
+        FILE* fmeta = fopen((ck_out + ".meta").c_str(), "w");
+        if (!fmeta || fprintf(fmeta, "%d\n", node.packages()) < 0 || fclose(fmeta) != 0) {
+          perror("checkpoint meta");
+          return 1;
+        }
+        fprintf(stderr, "checkpoint: %lld bytes after %d packages\n", bytes, node.packages());
+        ck_at = -1;
+        node.set_package_limit(-1);
+        n_step += node.spin();  // the packages the limit held back
+      }
       if (fm) {
         size_t at = 0;
         for (const int cnt : node.marker_scan_counts()) {

@@ -151,6 +151,11 @@ def lib():
         L.vg_stats_log.argtypes = [P, ctypes.POINTER(Stats), ctypes.c_int, ip]
         L.vg_release_far.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
         L.vg_window_states.argtypes = [P, dp, ip]
+        L.has_checkpoint = hasattr(L, "vg_checkpoint_save")  # a build older than the checkpoint (A/B runs)
+        if L.has_checkpoint:
+            L.vg_checkpoint_save.argtypes = [P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
+            L.vg_checkpoint_load.argtypes = [P, ctypes.c_char_p]
+            L.vgx_checkpoint_timed.argtypes = [P, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), dp]
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -383,6 +388,32 @@ class Context:
         out = (ctypes.c_longlong * 6)()
         self._chk(lib().vg_release_far(self.h, (1 if compact else 0) | (2 if census else 0), out), "vg_release_far")
         return list(out)
+
+    def _need_checkpoint(self):
+        if not lib().has_checkpoint:
+            raise VgError("this libvina_gpu.so has no checkpoint support (vg_checkpoint_save): rebuild it")
+
+    def checkpoint_save(self, path):
+        """Everything that outlives a scan to one file (vg_checkpoint_save; compacts first); returns its bytes."""
+        self._need_checkpoint()
+        n = ctypes.c_longlong(0)
+        self._chk(lib().vg_checkpoint_save(self.h, os.fsencode(path), ctypes.byref(n)), "vg_checkpoint_save")
+        return n.value
+
+    def checkpoint_load(self, path):
+        """Install a checkpoint into this context (vg_reset semantics first). A rejected file raises
+        VgError with the code (-1 VG_E_ARG, -3 VG_E_CAPACITY) and leaves the context as it was."""
+        self._need_checkpoint()
+        self._chk(lib().vg_checkpoint_load(self.h, os.fsencode(path)), "vg_checkpoint_load")
+
+    def checkpoint_timed(self, path, load=False):
+        """scripts/probe_checkpoint.py: (bytes, [4 phase times in ms]) of one save or load."""
+        self._need_checkpoint()
+        n = ctypes.c_longlong(0)
+        ms = np.zeros(4)
+        self._chk(lib().vgx_checkpoint_timed(self.h, os.fsencode(path), 1 if load else 0, ctypes.byref(n), _d(ms)),
+                  "vgx_checkpoint_timed")
+        return n.value, ms
 
     def window_states(self):
         out = np.zeros((64, STATE_LEN))

@@ -62,6 +62,9 @@ class VinaNode : public rclcpp::Node {
                  declare_parameter("General.pose_filename", std::string("trajectory.txt"));
     c.if_BA = (int)declare_parameter("General.if_BA", 0);
     const int enable_visualization = (int)declare_parameter("General.enable_visualization", 0);  // node.cpp:99-100
+    // checkpoint and resume (vg_checkpoint_save / vg_checkpoint_load): written at shutdown / loaded at start-up
+    checkpoint_path_ = declare_parameter("General.checkpoint_path", std::string(""));
+    const std::string resume_from = declare_parameter("General.resume_from", std::string(""));
     c.odo_cov_gyr = declare_parameter("Odometry.cov_gyr", 0.1);
     c.odo_cov_acc = declare_parameter("Odometry.cov_acc", 0.1);
     c.odo_rdw_gyr = declare_parameter("Odometry.rdw_gyr", 1e-4);
@@ -99,6 +102,7 @@ class VinaNode : public rclcpp::Node {
     fmt_.omega_l = 3610.0;
     vg_capacity cap = {0, 0, 0, 0};
     core_ = std::make_unique<vina_gpu::NodeCore>(c, &cap, fmt_, point_notime);
+    if (!resume_from.empty()) core_->load_checkpoint(resume_from);  // (a live node: no package to skip)
     if (enable_visualization) core_->enable_visualization(true);  // before the first scan
 
     rclcpp::QoS imu_qos(8000);
@@ -124,6 +128,13 @@ class VinaNode : public rclcpp::Node {
   }
 
   ~VinaNode() override {
+    if (!checkpoint_path_.empty()) {
+      try {
+        core_->save_checkpoint(checkpoint_path_);
+      } catch (const vina_gpu::Error& e) {
+        RCLCPP_ERROR(get_logger(), "checkpoint not written: %s", e.what());
+      }
+    }
     if (save_pose_ && !pose_file_.empty()) core_->write_tum(pose_file_);
   }
 
@@ -316,6 +327,7 @@ class VinaNode : public rclcpp::Node {
   int kind_ = 0;
   vg_lidar_format fmt_;
   bool save_pose_ = false;
+  std::string checkpoint_path_;
   std::string pose_file_;
   size_t published_ = 0;
   std::unique_ptr<vina_gpu::NodeCore> core_;
