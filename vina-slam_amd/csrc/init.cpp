@@ -90,15 +90,6 @@ static void imu_init(InitState& I, const std::vector<Imu>& imus) {
   }
 }
 
-static void put_frame(const HX& x, double* o) {  // kXS layout: R, p, v, bg, ba, g
-  memcpy(o, x.R.a, 72);
-  memcpy(o + 9, x.p.a, 24);
-  memcpy(o + 12, x.v.a, 24);
-  memcpy(o + 15, x.bg.a, 24);
-  memcpy(o + 18, x.ba.a, 24);
-  memcpy(o + 21, x.g.a, 24);
-}
-
 // ---- Initialization::motion_blur (initialization.cpp:64-156): the IMU poses
 // integrated backwards from the scan-end state xc with the biases of xl, in
 // the deskew record layout (t offset, R, p, v, w, a); list order = descending
@@ -249,7 +240,7 @@ struct GravLM {
   }
   std::vector<double> frames(const std::vector<HX>& xs) const {
     std::vector<double> f((size_t)W * kXS);
-    for (int i = 0; i < W; i++) put_frame(xs[i], &f[(size_t)i * kXS]);
+    for (int i = 0; i < W; i++) hx_put_frame(xs[i], &f[(size_t)i * kXS]);
     return f;
   }
   // give_evaluate_g (imu_preintegration.cpp:165-237): give_evaluate's residual
@@ -470,8 +461,7 @@ static void align_gravity(std::vector<HX>& xs) {
 
 static std::vector<double> frame_block(const HX& x) {  // kXC: frame state + covariance
   std::vector<double> b(kXC);
-  put_frame(x, b.data());
-  memcpy(b.data() + kXS, x.cov.a, 225 * sizeof(double));
+  hx_put_block(x, b.data());
   return b;
 }
 
@@ -500,7 +490,7 @@ static int motion_init(vg_ctx* ctx, HostPipe* P, InitState& I, int* rounds, int*
     VG_TRY(map_reset(ctx));
     {  // the window poses the recut's window view reads (DState::xs)
       std::vector<double> xs((size_t)W * kXS);
-      for (int i = 0; i < W; i++) put_frame(xb[i], &xs[(size_t)i * kXS]);
+      for (int i = 0; i < W; i++) hx_put_frame(xb[i], &xs[(size_t)i * kXS]);
       VG_TRY(state_load(ctx, xs.data(), W, nullptr, nullptr, 0));
     }
     for (int i = 0; i < W; i++) {
@@ -743,7 +733,7 @@ int init_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, co
   I.active = false;
   {
     std::vector<double> xs((size_t)W * kXS), recs((size_t)(W - 1) * kBaImuRec);
-    for (int i = 0; i < W; i++) put_frame(P->x_buf[i], &xs[(size_t)i * kXS]);
+    for (int i = 0; i < W; i++) hx_put_frame(P->x_buf[i], &xs[(size_t)i * kXS]);
     for (int k = 0; k < W - 1; k++) memcpy(&recs[(size_t)k * kBaImuRec], P->imu_pre[k].rec.data(), kBaImuRec * 8);
     const std::vector<double> xc = frame_block(P->x_curr);
     VG_TRY(state_load(ctx, xs.data(), W, xc.data(), recs.data(), W - 1));

@@ -1,25 +1,27 @@
 // pipeline.cpp — host side of the drop-in: the per-scan steady-state loop of
 // VINA_SLAM::thd_odometry_localmapping (local_mapping.cpp:389-547), reshaped
-// around device-resident stages. Host C++ keeps only what is O(IMU samples):
-// IMU propagation (imu_ekf.cpp:28-94) and preintegration
-// (imu_preintegration.cpp:31-95). Every per-point / per-voxel / per-factor
-// loop and the estimator state itself (x_curr, x_prop, x_buf, the IMU bias
-// records, the IEKF 15x15 update) live on the device (state.hip).
+// around device-resident stages: the stage entry points (one per reference
+// call) and the two fused step drivers that call them in reference order.
+// Host C++ keeps only what is O(IMU samples): IMU propagation (imu_ekf.cpp:28-94,
+// imu_prop.cpp) and preintegration (imu_preintegration.cpp:31-95, vg_host.h).
+// Every per-point / per-voxel / per-factor loop and the estimator state itself
+// (x_curr, x_prop, x_buf, the IMU bias records, the IEKF 15x15 update) live on
+// the device (state.hip).
 //
 // Asynchrony: a scan is enqueued without draining the stream. The host waits
 // only (a) for the downsampled point count, while the GPU runs the IEKF; (b)
 // for the recut's factor count; (c) for each LM iteration's flags, one
 // iteration ahead. The state the next scan's propagation needs is published to
 // host-mapped memory right after the BA, while the GPU still runs the margi;
-// the host mirror (x_curr, x_buf, trajectory, stats) absorbs it lazily.
+// the host mirror (x_curr, x_buf, trajectory, stats) absorbs it lazily
+// (host_mirror.cpp).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
+#include <functional>
 #include <vector>
 
-#include "ckpt_file.h"
 #include "vg_host.h"
 
 namespace vg {
@@ -31,359 +33,21 @@ static int flush_begin(vg_ctx* ctx, HostPipe* P) {
   return P->begin_prop ? state_scan_begin(ctx, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &P->prop)
                        : state_scan_begin(ctx, P->begin_xc);
 }
-static int flush_deferred(vg_ctx* ctx, HostPipe* P) {
-  VG_TRY(flush_begin(ctx, P));
+static int flush_push(vg_ctx* ctx, HostPipe* P) {
   if (!P->push_pending) return VG_OK;
   P->push_pending = false;
   return state_push(ctx, P->push.ord, P->push.new_imu, P->push.rec);
 }
-
-
-void host_init(vg_ctx* ctx) {
-  HostPipe* P = new HostPipe();
-  const vg_config& c = ctx->cfg;
-  P->mp.resize(c.win_size);
-  for (int i = 0; i < c.win_size; i++) P->mp[i] = i;
-  MP& m = P->mpd;
-  memset(&m, 0, sizeof(m));
-  m.vs = c.voxel_size;
-  m.min_eig = c.min_eigen_value;
-  for (int i = 0; i < 4; i++) {
-    m.thre[i] = 1.0 / c.plane_eigen_value_thre[i];
-    m.minpt[i] = c.min_point[i];
-  }
-  for (int i = 0; i < 9; i++) m.extR[i] = c.ext_R[i];
-  for (int i = 0; i < 3; i++) m.extt[i] = c.ext_t[i];
-  m.dept = (float)c.dept_err;
-  m.beam = (float)c.beam_err;
-  {
-    const double sb = sin(m.beam * M_PI / 180.0);  // calcBodyVar's (float degree_inc) * M_PI / 180.0
-    m.beam_dv = sb * sb;
-  }
-  m.max_layer = c.max_layer;
-  m.max_points = c.max_points;
-  m.W = c.win_size;
-  for (int i = 0; i < 3; i++) {
-    P->noiseMeas(i, i) = c.ba_cov_gyr;
-    P->noiseMeas(3 + i, 3 + i) = c.ba_cov_acc;
-    P->noiseWalk(i, i) = c.ba_rdw_gyr;
-    P->noiseWalk(3 + i, 3 + i) = c.ba_rdw_acc;
-  }
-  P->sg = gravity_scale(c);
-  if (c.cold_start) P->init = init_create(ctx);
-  ctx->host = P;
-}
-void host_free(vg_ctx* ctx) {
-  if (hp(ctx) && hp(ctx)->init) init_destroy(hp(ctx)->init);
-  delete hp(ctx);
-  ctx->host = nullptr;
-}
-void host_reset(vg_ctx* ctx) {
-  host_free(ctx);
-  host_init(ctx);
+int flush_deferred(vg_ctx* ctx, HostPipe* P) {
+  VG_TRY(flush_begin(ctx, P));
+  return flush_push(ctx, P);
 }
 
-// ---- absorbing published device results into the host mirror
-
-static int map_error(vg_ctx* ctx, int e) {
-  ctx->err = std::string("device map error flags=") + std::to_string(e) + ((e & 4) ? " (node pool full)" : "") +
-             ((e & 8) ? " (point_fix arena full)" : "") + ((e & 1) ? " (voxel key out of packed range)" : "") +
-             ((e & 2) ? " (root hash full)" : "") + ((e & 16) ? " (subdivision event buffer full)" : "") +
-             ((e & 32) ? " (sharded exchange out of step: the ranks' exchange sequences differ)" : "") +
-             ((e & 64) ? " (cross-stream hand-off timed out)" : "");
-  if (e & (32 | 64)) return VG_E_STATE;  // out-of-step exchange, or a hand-off that timed out: not a capacity limit
-  return (e & 1) ? VG_E_RANGE : VG_E_CAPACITY;
-}
-
-// LioStateEstimation's return value (odometry.cpp:244-254): lambda_min of
-// sum n n^T >= 14; bookkeeping only (degrade_cnt, local_mapping.cpp:413-423)
-static int degenerate_of(const double* nnt) {
-  M3 nn;
-  nn(0, 0) = nnt[0];
-  nn(0, 1) = nn(1, 0) = nnt[1];
-  nn(0, 2) = nn(2, 0) = nnt[2];
-  nn(1, 1) = nnt[3];
-  nn(1, 2) = nn(2, 1) = nnt[4];
-  nn(2, 2) = nnt[5];
-  V3 ev;
-  M3 U;
-  eig3(nn, ev, U);
-  return (ev[0] < 14) ? 1 : 0;
-}
-
-// P1 of the oldest pending scan: x_curr, post-IEKF pose, window states
-static int absorb_p1(vg_ctx* ctx, HostPipe* P, Pend& q) {
-  if (q.seq1 == 0) return VG_OK;
-  VG_TRY(pub_wait(ctx, &ctx->h_pub->seq1, q.seq1, "state publication"));
-  const Pub& pb = *ctx->h_pub;
-  HX& xc = P->x_curr;
-  memcpy(xc.R.a, pb.xc, 72);
-  memcpy(xc.p.a, pb.xc + 9, 24);
-  memcpy(xc.v.a, pb.xc + 12, 24);
-  memcpy(xc.bg.a, pb.xc + 15, 24);
-  memcpy(xc.ba.a, pb.xc + 18, 24);
-  memcpy(xc.g.a, pb.xc + 21, 24);
-  memcpy(xc.cov.a, pb.xc + kXS, 225 * sizeof(double));
-  for (size_t i = 0; i < P->x_buf.size(); i++) {
-    const double* o = pb.xs + (i + q.shift) * kXS;
-    HX& h = P->x_buf[i];
-    memcpy(h.R.a, o, 72);
-    memcpy(h.p.a, o + 9, 24);
-    memcpy(h.v.a, o + 12, 24);
-    memcpy(h.bg.a, o + 15, 24);
-    memcpy(h.ba.a, o + 18, 24);
-    memcpy(h.g.a, o + 21, 24);
-  }
-  if (q.pushed >= 0 && q.pushed < (int)P->x_buf.size()) P->x_buf[q.pushed].cov = xc.cov;
-  if (!q.init_tail) {  // pub_localtraj's path point and save_pose_tum's row (local_mapping.cpp:427-430)
-    P->traj.push_back(q.t);
-    for (int i = 0; i < 12; i++) P->traj.push_back(pb.traj[i]);
-    P->path.push_back(q.t);
-    for (int i = 0; i < 12; i++) P->path.push_back(pb.traj[i]);
-    P->path.push_back(P->jour);
-    q.st.iekf_iters = pb.iekf_iters;
-    for (int i = 0; i < 4; i++) q.st.iekf_matches[i] = pb.matches[i];
-    q.st.iekf_points = pb.iekf_pts;
-    q.st.degenerate = degenerate_of(pb.nnt);
-  }
-  q.st.ba_iters = pb.ba_iters1;
-  q.st.ba_hess = pb.ba_hess1;
-  for (int i = 0; i < 4; i++) q.st.iekf_planes[i] = pb.planes[i];
-  if (q.shift) {  // pub_localmap (publishers.cpp:121-129, local_mapping.cpp:505): the window's path rows
-                  // [win_base, win_base + win_count) take x_buf[i].p after the BA (pb.xs: the window before the slide)
-    const int W = ctx->cfg.win_size;
-    const int rows = (int)P->path.size() / kPathRow;
-    if (rows >= W)
-      for (int i = 0; i < W; i++) memcpy(&P->path[(size_t)(rows - W + i) * kPathRow + 10], pb.xs + (size_t)i * kXS + 9, 24);
-  }
-  if (q.jour_check) {  // local_mapping.cpp:525-533 with x_curr.p = x_buf.back().p after the BA
-    double spat = norm3(sub(xc.p, P->last_pos));
-    if (spat > 0.5) {
-      P->jour += spat;
-      P->last_pos = xc.p;
-      P->release_flag = true;
-    }
-  }
-  q.seq1 = 0;
-  return VG_OK;
-}
-
-// k_iekf launches of the executed IEKF iterations (vg_profile bit 0)
-static void collect_iekf_events(vg_ctx* ctx, const Pend& q) {
-  for (int r = 0; r < q.ev_n && r < q.st.iekf_iters; r++) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->iekf_ev[q.ev_base + r][0], ctx->iekf_ev[q.ev_base + r][1]) == hipSuccess) {
-      ctx->prof_ms[kProfIekfKernel] += ms;
-      ctx->prof_n[kProfIekfKernel] += 1;
-    }
-  }
-}
-
-// P2: end-of-scan counters; the scan's stats are complete
-static int absorb_p2(vg_ctx* ctx, HostPipe* P, Pend& q) {
-  VG_TRY(absorb_p1(ctx, P, q));
-  VG_TRY(pub_wait(ctx, &ctx->h_pub->seq2, q.seq2, "counter publication"));
-  const int* c = ctx->h_pub->counters;
-  q.st.n_slide = c[kCntSlide];
-  q.st.nodes_used = c[kCntNodes];
-  q.st.fix_used = c[kCntFix];
-  if (!q.init_tail) q.st.roots_new = c[kCntRoots];  // init: the rebuilt map's roots (init.cpp)
-  q.st.plane_updates = c[kCntPlaneUpd];
-  if (!q.init_tail) {  // the insert's downsampled count (the insert read it on the device)
-    q.st.n_ds = c[kCntNds];
-    if (q.ins_slot >= 0) P->wp_n[q.ins_slot] = c[kCntNds];
-  }
-  q.st.fix_full = c[kCntFixFull];
-  q.st.v_ins = c[kCntSeg];
-  // events recorded while this scan was enqueued are complete now
-  collect_iekf_events(ctx, q);
-  for (int i = 0; i < kProfN; i++)
-    if (ctx->prof_pending[i] && i != kProfIekfKernel) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->prof_ev[i][0], ctx->prof_ev[i][1]) == hipSuccess) {
-        ctx->prof_ms[i] += ms;
-        ctx->prof_n[i] += 1;
-      }
-      ctx->prof_pending[i] = false;
-    }
-  ctx->stats = q.st;
-  P->stats_log.push_back(q.st);
-  if (c[kCntErr]) return map_error(ctx, c[kCntErr]);
-  return VG_OK;
-}
-
-// The outcome of the previous fused step's LM (stage_ba left it pending):
-// ba_resolve waits for its flags and enqueues any further iteration; if the
-// speculative margi tail did not run, the real one follows with the same
-// publication numbers and window view, so every wait already enqueued on
-// those numbers (the next IEKF's hand-off flags, the host's P1 / P2) holds.
-// block = false: returns without waiting when a flag is not published yet.
-static int resolve_lm(vg_ctx* ctx, HostPipe* P, bool block = true) {
-  if (!P->lmp.active) return VG_OK;
-  HostTimer ht_(ctx, kHostBA);
-  bool fin = true, tail_ok = true;
-  int iters = 0;
-  int r = ba_resolve(ctx, block, &fin, &iters, &tail_ok);
-  if (r == VG_OK && !fin) return VG_OK;
-  P->lmp.active = false;
-  if (r == VG_OK && !tail_ok)
-    r = map_margi(ctx, P->mpd, P->lmp.wa, 0, ctx->cfg.thread_num, P->lmp.seq1, P->lmp.seq2, nullptr);
-  if (r != VG_OK) P->sticky = r;
-  return r;
-}
-
-// absorb every pending scan whose results are needed (all of P1, and P2 when
-// `full`); blocking
-int absorb(vg_ctx* ctx, HostPipe* P, bool full) {
-  if (P->sticky != VG_OK) return P->sticky;
-  VG_TRY(resolve_lm(ctx, P));
-  int r = VG_OK;
-  while (!P->pend.empty()) {
-    Pend& q = P->pend.front();
-    r = full || P->pend.size() > 1 ? absorb_p2(ctx, P, q) : absorb_p1(ctx, P, q);
-    if (r != VG_OK) break;
-    if (q.seq1 == 0 && (full || P->pend.size() > 1)) {
-      P->pend.pop_front();
-    } else {
-      break;
-    }
-  }
-  if (r != VG_OK) P->sticky = r;
-  return r;
-}
-
-// non-blocking: absorb, oldest first, every pending scan whose publications
-// (state and end-of-scan counters) have both arrived; stops at the first that
-// has not. Only the newest pending scan can be unpublished (the host absorbs a
-// scan's state before the next scan publishes), so the Pub block holds the
-// scan being absorbed.
-int absorb_ready(vg_ctx* ctx, HostPipe* P) {
-  if (P->sticky != VG_OK) return P->sticky;
-  VG_TRY(resolve_lm(ctx, P, false));
-  if (P->lmp.active) return VG_OK;  // the LM is still running: nothing of that scan is published
-  while (!P->pend.empty()) {
-    Pend& q = P->pend.front();
-    if (q.seq1 != 0 && __atomic_load_n(&ctx->h_pub->seq1, __ATOMIC_ACQUIRE) < q.seq1) break;
-    if (__atomic_load_n(&ctx->h_pub->seq2, __ATOMIC_ACQUIRE) < q.seq2) break;
-    const int r = absorb_p2(ctx, P, q);
-    if (r != VG_OK) {
-      P->sticky = r;
-      return r;
-    }
-    P->pend.pop_front();
-  }
-  return VG_OK;
-}
-
-int host_sync(vg_ctx* ctx) {
-  HostPipe* P = hp(ctx);
-  if (P->in_scan) {
-    ctx->err = "host_sync inside a scan";
-    return VG_E_STATE;
-  }
-  VG_TRY(resolve_lm(ctx, P));  // before the drain: it may enqueue work
-  VG_HIP(stream_wait(ctx));
-  return absorb(ctx, P, true);
-}
-
-// IMUEKF::motion_blur state/covariance propagation (imu_ekf.cpp:28-94); the
-// per-point deskew (114-144) is SURVEY row f1 (callers pass compensated scans).
-// one row of a sparse 15x15 matrix: its non-zero columns, ascending
-struct SpRow {
-  int n;
-  int k[7];
-  double v[7];
-};
-// F C F^T + Q with F given by its rows; every sum in ascending column order
-// (the dense product's order, zero terms dropped)
-static M15 sandwich(const SpRow* F, const M15& C, const M15& Q) {
-  M15 A, out;
-  for (int i = 0; i < 15; i++)
-    for (int j = 0; j < 15; j++) {
-      double s = F[i].v[0] * C(F[i].k[0], j);
-      for (int t = 1; t < F[i].n; t++) s += F[i].v[t] * C(F[i].k[t], j);
-      A(i, j) = s;
-    }
-  for (int i = 0; i < 15; i++)
-    for (int j = 0; j < 15; j++) {
-      double s = A(i, F[j].k[0]) * F[j].v[0];
-      for (int t = 1; t < F[j].n; t++) s += A(i, F[j].k[t]) * F[j].v[t];
-      out(i, j) = s + Q(i, j);
-    }
-  return out;
-}
-
-void propagate(vg_ctx* ctx, HostPipe* P, const std::vector<Imu>& imus, double pcl_beg, double pcl_end) {
-  P->poses.clear();
-  const vg_config& c = ctx->cfg;
-  HX& xc = P->x_curr;
-  V3 acc_imu = V3::Z(), angvel = V3::Z(), acc_avr, vel = xc.v, pos = xc.p;
-  M3 R_imu = xc.R;
-  double dt = 0;
-  for (size_t k = 0; k + 1 < imus.size(); k++) {
-    const Imu& head = imus[k];
-    const Imu& tail = imus[k + 1];
-    if (head.t < P->last_pcl_end_time) continue;
-    for (int j = 0; j < 3; j++) {
-      angvel[j] = 0.5 * (head.gyr[j] + tail.gyr[j]);
-      acc_avr[j] = 0.5 * (head.acc[j] + tail.acc[j]);
-    }
-    angvel = sub(angvel, xc.bg);
-    acc_avr = sub(scl(acc_avr, P->sg), xc.ba);  // imu_ekf.cpp:51
-    acc_imu = add(mul(R_imu, acc_avr), xc.g);
-    double cur = head.t;
-    if (cur < P->last_pcl_end_time) cur = P->last_pcl_end_time;
-    dt = tail.t - cur;
-    {  // imu_poses.emplace_back(offt, R_imu, pos_imu, vel_imu, angvel_avr, acc_imu) (imu_ekf.cpp:64)
-      double rec[22];
-      rec[0] = cur - pcl_beg;
-      memcpy(rec + 1, R_imu.a, 72);
-      memcpy(rec + 10, pos.a, 24);
-      memcpy(rec + 13, vel.a, 24);
-      memcpy(rec + 16, angvel.a, 24);
-      memcpy(rec + 19, acc_imu.a, 24);
-      P->poses.insert(P->poses.end(), rec, rec + 22);
-    }
-    M3 ask = hat(acc_avr);
-    M3 Exp_f = Exp(angvel, dt);
-    M15 cw = M15::Z();
-    M3 F00 = Exp(angvel, -dt), F60 = scl(mul(R_imu, ask), -dt), F612 = scl(R_imu, -dt);
-    M3 ca = M3::Z();
-    for (int j = 0; j < 3; j++) ca(j, j) = c.odo_cov_acc;
-    M3 cw66 = scl(mul(mul(R_imu, ca), tr(R_imu)), dt * dt);
-    for (int r = 0; r < 3; r++) {
-      for (int q = 0; q < 3; q++) cw(6 + r, 6 + q) = cw66(r, q);
-      cw(r, r) = c.odo_cov_gyr * dt * dt;
-      cw(9 + r, 9 + r) = c.odo_rdw_gyr * dt * dt;
-      cw(12 + r, 12 + r) = c.odo_rdw_acc * dt * dt;
-    }
-    // cov = F cov F^T + cw (imu_ekf.cpp:79) with F's non-zeros only: F is the
-    // identity but for rows 0-2 (F00, -dt I), 3-5 (I, dt I) and 6-8 (F60, I,
-    // F612). Terms are summed in ascending column order, as the dense product
-    // does, and the zero terms it adds are exact no-ops: same bits, 5x fewer
-    // flops on the host's per-scan critical path.
-    SpRow Fr[15];
-    for (int r = 0; r < 3; r++) {
-      Fr[r] = SpRow{4, {0, 1, 2, 9 + r}, {F00(r, 0), F00(r, 1), F00(r, 2), -dt}};
-      Fr[3 + r] = SpRow{2, {3 + r, 6 + r}, {1.0, dt}};
-      Fr[6 + r] = SpRow{7, {0, 1, 2, 6 + r, 12, 13, 14}, {F60(r, 0), F60(r, 1), F60(r, 2), 1.0, F612(r, 0),
-                                                           F612(r, 1), F612(r, 2)}};
-    }
-    for (int r = 9; r < 15; r++) Fr[r] = SpRow{1, {r}, {1.0}};
-    xc.cov = sandwich(Fr, xc.cov, cw);
-    pos = add(add(pos, scl(vel, dt)), scl(acc_imu, 0.5 * dt * dt));
-    vel = add(vel, scl(acc_imu, dt));
-    R_imu = mul(R_imu, Exp_f);
-  }
-  if (!imus.empty()) {
-    double note = pcl_end > imus.back().t ? 1.0 : -1.0;
-    dt = note * (pcl_end - imus.back().t);
-    xc.v = add(vel, scl(acc_imu, note * dt));
-    xc.R = mul(R_imu, Exp(scl(angvel, note), dt));
-    xc.p = add(add(pos, scl(vel, note * dt)), scl(acc_imu, note * 0.5 * dt * dt));
-  }
-  xc.t = pcl_end;
-  P->last_pcl_end_time = pcl_end;
+// host_step's early downsample (HostPipe::ds_hook), taken out so that it runs once
+static std::function<int()> take_ds_hook(HostPipe* P) {
+  std::function<int()> h = std::move(P->ds_hook);
+  P->ds_hook = nullptr;
+  return h;
 }
 
 // LioStateEstimation (odometry.cpp:64-255) with use_vnc = true (4 iterations),
@@ -392,19 +56,15 @@ void propagate(vg_ctx* ctx, HostPipe* P, const std::vector<Imu>& imus, double pc
 // device. The VNC scan-plane prep (84-96, 150-190) contributes nothing
 // (SURVEY finding 3: matchVoxelMap always returns 0) and is skipped as
 // output-invariant.
-static int flush_deferred_push(vg_ctx* ctx, HostPipe* P) {
-  if (!P->push_pending) return VG_OK;
-  VG_TRY(flush_begin(ctx, P));
-  P->push_pending = false;
-  return state_push(ctx, P->push.ord, P->push.new_imu, P->push.rec);
-}
 static int lio_state_estimation(vg_ctx* ctx, HostPipe* P, const float* x, const float* y, const float* z, int n) {
   // event pairs alternate between two banks: scan k's are collected while
   // scan k+1 is being enqueued
   ctx->iekf_ring_base = ctx->iekf_ring_base == 0 ? 8 : 0;
   P->cur.ev_base = ctx->iekf_ring_base;
   P->cur.ev_n = (ctx->prof_on && (ctx->prof_stages || !ctx->use_graphs || sharded(ctx))) ? 4 : 0;
-  VG_TRY(flush_deferred_push(ctx, P));
+  // a pending push goes out on its own, behind the opening it belongs to. A
+  // pending opening alone stays: this IEKF's first launch carries it (below)
+  if (P->push_pending) VG_TRY(flush_deferred(ctx, P));
   const bool begin = P->begin_pending;
   P->begin_pending = false;
   // behind the previous margi's plane updates only (map_margi): its
@@ -419,10 +79,8 @@ static int lio_state_estimation(vg_ctx* ctx, HostPipe* P, const float* x, const 
   // host_step's early downsample: enqueued behind this IEKF's launches when
   // those go out without a host wait (below), else first
   auto ds_hook = [&]() -> int {
-    if (!P->ds_hook) return VG_OK;
-    const std::function<int()> h = std::move(P->ds_hook);
-    P->ds_hook = nullptr;
-    return h();
+    const std::function<int()> h = take_ds_hook(P);
+    return h ? h() : VG_OK;
   };
   // a pending LM is resolved before this IEKF is enqueued unless the IEKF
   // stream waits for the margi on device flags (the numbers the real tail
@@ -553,15 +211,7 @@ int stage_propagate(vg_ctx* ctx, const double* imu, int m, double beg, double en
       P->x_curr.t = end;
       P->last_pcl_end_time = end;
     }
-    double* xc = P->begin_xc;  // opened on the device with the IEKF's first launch (flush_begin otherwise)
-    const HX& h = P->x_curr;
-    memcpy(xc, h.R.a, 72);
-    memcpy(xc + 9, h.p.a, 24);
-    memcpy(xc + 12, h.v.a, 24);
-    memcpy(xc + 15, h.bg.a, 24);
-    memcpy(xc + 18, h.ba.a, 24);
-    memcpy(xc + 21, h.g.a, 24);
-    memcpy(xc + kXS, h.cov.a, 225 * sizeof(double));
+    hx_put_block(P->x_curr, P->begin_xc);  // opened on the device with the IEKF's first launch (flush_begin otherwise)
   }
   P->begin_pending = true;
   P->push_pending = false;
@@ -595,10 +245,6 @@ static int resolve_ds(vg_ctx* ctx, HostPipe* P) {
   return VG_OK;
 }
 
-// down_sampling_voxel(pl_down, down_size) and its /2 fallback below 2000
-// voxels (local_mapping.cpp:396-403), both decided on the device
-// (ds_enqueue_hashed): the host never waits for the count, the GPU runs the
-// IEKF meanwhile and the insert reads the count where it lands
 // the downsample's device work on its own stream, which waits only until the
 // previous insert has read the ds buffers (and for a deskewed scan)
 static int ds_enqueue_scan(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, int n,
@@ -633,6 +279,10 @@ static void ds_adopt(HostPipe* P, const float* dx, const float* dy, const float*
   P->ds_n = -1;
 }
 
+// down_sampling_voxel(pl_down, down_size) and its /2 fallback below 2000
+// voxels (local_mapping.cpp:396-403), both decided on the device
+// (ds_enqueue_hashed): the host never waits for the count, the GPU runs the
+// IEKF meanwhile and the insert reads the count where it lands
 int stage_downsample(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, int n,
                      int* n_ds_out) {
   HostTimer ht_(ctx, kHostDownsample);
@@ -699,6 +349,14 @@ int stage_window_push(vg_ctx* ctx, const double* imu, int m) {
   return VG_OK;
 }
 
+// the scan's insert is enqueued: the window slot it filled and that slot's point count
+static void insert_done(HostPipe* P, int slot) {
+  P->wp_n[slot] = P->n_raw;  // an upper bound until the scan's counters are absorbed (absorb_p2)
+  P->ins_slot = slot;
+  P->cur.ins_slot = slot;
+  P->ins_n = -1;
+}
+
 // pvec_update + cut_voxel_multi of the downsampled scan (local_mapping.cpp:425-448)
 int stage_insert(vg_ctx* ctx) {
   HostTimer ht_(ctx, kHostInsert);
@@ -728,10 +386,7 @@ int stage_insert(vg_ctx* ctx) {
   prof_end(ctx, kProfInsert);
   VG_HIP(hipEventRecord(ctx->ev_ds_free, ctx->stream));  // the insert has read the ds buffers
   ctx->ds_free_ev = ctx->ev_ds_free;
-  P->wp_n[slot] = P->n_raw;  // an upper bound until the scan's counters are absorbed (absorb_p2)
-  P->ins_slot = slot;
-  P->cur.ins_slot = slot;
-  P->ins_n = -1;
+  insert_done(P, slot);
   return VG_OK;
 }
 
@@ -843,32 +498,24 @@ static int stage_insert_recut(vg_ctx* ctx) {
   prof_begin(ctx, kProfInsert);
   VG_HIP(hipGraphLaunch(ge, ctx->stream));
   prof_end(ctx, kProfInsert);
-  // the insert + recut graph's asynchronous recut leaves tras_opt's factor
-  // bookkeeping to the LM's k_ba_init (the scan graph holds that k_ba_init)
-  if (!sg) ctx->rc_finish_in_init = ctx->rc_init_finish;
   if (sg) {  // nothing to record: the prefix and the next downsample order themselves on the flags
     ctx->ins_ev_pending = false;
     ctx->tail_a_valid = true;  // the next IEKF waits for this graph's tail (device flags)
-    P->wp_n[slot] = P->n_raw;
-    P->ins_slot = slot;
-    P->cur.ins_slot = slot;
-    P->ins_n = -1;
-    P->rc_seq = ++ctx->rc_pub;
-    return VG_OK;
+  } else {
+    // the insert + recut graph's asynchronous recut leaves tras_opt's factor
+    // bookkeeping to the LM's k_ba_init (the scan graph holds that k_ba_init)
+    ctx->rc_finish_in_init = ctx->rc_init_finish;
+    // ev_ds_free (the insert has read the ds buffers) and ev_recut_done (the
+    // margi prefix starts from here): recorded by their first waiter's flush,
+    // the LM's right behind k_ba_init (a record right behind the graph leaves
+    // the stream idle before k_ba_init). With the early downsample the next
+    // scan's downsample is enqueued after this LM anyway; without it the
+    // records stay right behind the graph, so that downsample does not wait
+    // for k_ba_init.
+    ctx->ins_ev_pending = true;
+    if (!ctx->ds_early) VG_HIP(flush_insert_events(ctx));
   }
-  // ev_ds_free (the insert has read the ds buffers) and ev_recut_done (the
-  // margi prefix starts from here): recorded by their first waiter's flush,
-  // the LM's right behind k_ba_init (a record right behind the graph leaves
-  // the stream idle before k_ba_init). With the early downsample the next
-  // scan's downsample is enqueued after this LM anyway; without it the
-  // records stay right behind the graph, so that downsample does not wait
-  // for k_ba_init.
-  ctx->ins_ev_pending = true;
-  if (!ctx->ds_early) VG_HIP(flush_insert_events(ctx));
-  P->wp_n[slot] = P->n_raw;  // an upper bound until the scan's counters are absorbed (absorb_p2)
-  P->ins_slot = slot;
-  P->cur.ins_slot = slot;
-  P->ins_n = -1;
+  insert_done(P, slot);
   P->rc_seq = ++ctx->rc_pub;  // k_fac_sort in the graph publishes the same number
   return VG_OK;
 }
@@ -1088,8 +735,6 @@ int stage_finish(vg_ctx* ctx) {
   return VG_OK;
 }
 
-int host_win_count(vg_ctx* ctx) { return hp(ctx)->win_count; }
-
 // for a read of the map (vg_map_planes): between scans everything outstanding;
 // inside a stage-level scan the main stream, which carries every map write of
 // the stages called so far
@@ -1142,9 +787,9 @@ int stage_deskew(vg_ctx* ctx, const float* x, const float* y, const float* z, co
   VG_TRY(need_open(ctx, P, "vg_deskew"));
   const int npose = (int)P->poses.size() / 22;
   std::vector<double> par(24 + P->poses.size());
-  const HX& xc = P->x_curr;
-  memcpy(par.data(), xc.R.a, 72);
-  memcpy(par.data() + 9, xc.p.a, 24);
+  double f[kXS];
+  hx_put_frame(P->x_curr, f);
+  memcpy(par.data(), f, 12 * sizeof(double));  // R, p: the head of the frame
   for (int i = 0; i < 9; i++) par[12 + i] = ctx->cfg.ext_R[i];
   for (int i = 0; i < 3; i++) par[21 + i] = ctx->cfg.ext_t[i];
   if (!P->poses.empty()) memcpy(par.data() + 24, P->poses.data(), P->poses.size() * sizeof(double));
@@ -1154,34 +799,11 @@ int stage_deskew(vg_ctx* ctx, const float* x, const float* y, const float* z, co
   return VG_OK;
 }
 
-// one scan with the deskew: the rest of the pipeline reads the staging buffers
-int host_step_deskew(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di,
-                     const float* dt, int n, double beg, double end, const double* imu, int m) {
-  const vg_config& c = ctx->cfg;
-  if (init_active(hp(ctx))) return init_step(ctx, dx, dy, dz, di, dt, n, beg, end, imu, m);
-  VG_TRY(stage_propagate(ctx, imu, m, beg, end));
-  VG_TRY(stage_deskew(ctx, dx, dy, dz, di, dt, n));
-  const float *x = ctx->d_x, *y = ctx->d_y, *z = ctx->d_z, *i = ctx->d_i;
-  VG_TRY(stage_iekf(ctx, x, y, z, n, nullptr));
-  VG_TRY(stage_downsample(ctx, x, y, z, i, n, nullptr));
-  VG_TRY(stage_window_push(ctx, imu, m));
-  if (mid_graph_ok(ctx, hp(ctx))) {
-    VG_TRY(stage_insert_recut(ctx));
-  } else {
-    VG_TRY(stage_insert(ctx));
-    VG_TRY(stage_recut(ctx, nullptr));
-  }
-  if (hp(ctx)->win_count >= c.win_size) {
-    if (c.if_BA == 1) VG_TRY(stage_ba(ctx, nullptr, true));
-    VG_TRY(stage_margi_slide(ctx));
-  }
-  return stage_finish(ctx);
-}
-
 // slack probe (scripts/slack_probe.sh): VG_HOST_DELAY="point,us" busy-waits
 // the host at one point of the step; ms/scan rises by the delay only where the
 // host is on the critical path (0: before the IEKF, 1: before the LM, 2: after
-// the LM wait, 3: before the insert, 4: before the downsample)
+// the LM wait, 3: before the insert, 4: before the downsample, 5: at the start
+// of the step)
 static void host_delay(int point) {
   static int p = -2, us = 0;
   if (p == -2) {
@@ -1195,10 +817,47 @@ static void host_delay(int point) {
   }
 }
 
+// what both fused steps do once the IEKF and the downsample are enqueued
+// (local_mapping.cpp:434-546): the window push, the insert + recut (as one
+// graph where that holds), the BA and the margi once the window is full, and
+// the end of the scan
+static int step_tail(vg_ctx* ctx, const double* imu, int m) {
+  const vg_config& c = ctx->cfg;
+  HostPipe* P = hp(ctx);
+  VG_TRY(stage_window_push(ctx, imu, m));
+  host_delay(3);
+  if (mid_graph_ok(ctx, P)) {
+    VG_TRY(stage_insert_recut(ctx));
+  } else {
+    VG_TRY(stage_insert(ctx));
+    VG_TRY(stage_recut(ctx, nullptr));
+  }
+  if (P->win_count >= c.win_size) {
+    host_delay(1);
+    if (c.if_BA == 1) VG_TRY(stage_ba(ctx, nullptr, true));
+    host_delay(2);
+    VG_TRY(stage_margi_slide(ctx));
+  }
+  return stage_finish(ctx);
+}
+
+// one scan with the deskew: the rest of the pipeline reads the staging
+// buffers. The propagation runs on the host (the deskew needs its IMU poses),
+// and the downsample follows the IEKF, on the deskewed scan
+int host_step_deskew(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di,
+                     const float* dt, int n, double beg, double end, const double* imu, int m) {
+  if (init_active(hp(ctx))) return init_step(ctx, dx, dy, dz, di, dt, n, beg, end, imu, m);
+  VG_TRY(stage_propagate(ctx, imu, m, beg, end));
+  VG_TRY(stage_deskew(ctx, dx, dy, dz, di, dt, n));
+  const float *x = ctx->d_x, *y = ctx->d_y, *z = ctx->d_z, *i = ctx->d_i;
+  VG_TRY(stage_iekf(ctx, x, y, z, n, nullptr));
+  VG_TRY(stage_downsample(ctx, x, y, z, i, n, nullptr));
+  return step_tail(ctx, imu, m);
+}
+
 // one scan of thd_odometry_localmapping's steady-state branch
 int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, int n, double beg,
               double end, const double* imu, int m) {
-  const vg_config& c = ctx->cfg;
   if (init_active(hp(ctx))) return init_step(ctx, dx, dy, dz, di, nullptr, n, beg, end, imu, m);
   // both read only the raw scan (local_mapping.cpp:396-413). The downsample
   // (its count stays on the device) goes first, on its own stream, before the
@@ -1221,11 +880,8 @@ int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, co
   VG_TRY(stage_propagate(ctx, imu, m, beg, end, true));
   host_delay(0);
   const int r_iekf = stage_iekf(ctx, dx, dy, dz, n, nullptr);
-  if (P->ds_hook) {  // not run inside (an error, or a path without the IEKF's enqueue)
-    const std::function<int()> h = std::move(P->ds_hook);
-    P->ds_hook = nullptr;
-    if (r_iekf == VG_OK) VG_TRY(h());
-  }
+  // the hook did not run inside (an error, or a path without the IEKF's enqueue)
+  if (const std::function<int()> h = take_ds_hook(P); h && r_iekf == VG_OK) VG_TRY(h());
   VG_TRY(r_iekf);
   host_delay(4);
   if (early) {
@@ -1234,363 +890,7 @@ int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, co
   } else {
     VG_TRY(stage_downsample(ctx, dx, dy, dz, di, n, nullptr));
   }
-  VG_TRY(stage_window_push(ctx, imu, m));
-  host_delay(3);
-  if (mid_graph_ok(ctx, hp(ctx))) {
-    VG_TRY(stage_insert_recut(ctx));
-  } else {
-    VG_TRY(stage_insert(ctx));
-    VG_TRY(stage_recut(ctx, nullptr));
-  }
-  if (hp(ctx)->win_count >= c.win_size) {
-    host_delay(1);
-    if (c.if_BA == 1) VG_TRY(stage_ba(ctx, nullptr, true));
-    host_delay(2);
-    VG_TRY(stage_margi_slide(ctx));
-  }
-  return stage_finish(ctx);
-}
-
-void host_seed(vg_ctx* ctx, const double* s) {
-  HX& x = hp(ctx)->x_curr;
-  x.t = s[0];
-  memcpy(x.R.a, s + 1, 72);
-  memcpy(x.p.a, s + 10, 24);
-  memcpy(x.v.a, s + 13, 24);
-  memcpy(x.bg.a, s + 16, 24);
-  memcpy(x.ba.a, s + 19, 24);
-  memcpy(x.g.a, s + 22, 24);
-  memcpy(x.cov.a, s + 25, 225 * sizeof(double));
-}
-static void state_out(const HX& x, double* s) {
-  s[0] = x.t;
-  memcpy(s + 1, x.R.a, 72);
-  memcpy(s + 10, x.p.a, 24);
-  memcpy(s + 13, x.v.a, 24);
-  memcpy(s + 16, x.bg.a, 24);
-  memcpy(s + 19, x.ba.a, 24);
-  memcpy(s + 22, x.g.a, 24);
-  memcpy(s + 25, x.cov.a, 225 * sizeof(double));
-}
-// lio_state_estimation_kdtree (odometry.cpp:267-439) on an
-// explicit state (250 doubles in/out): the per-point kNN, plane fit and
-// normal-equation sums on the device (kdlio.hip), the 15x15 update here. The
-// scan is the init-phase cloud downsampled at max(down_size, 0.5), raw LiDAR
-// frame (xyz AoS). *valid = -1 when the map held < 100 points and the scan
-// only seeded it.
-int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters) {
-  VG_TRY(host_sync(ctx));  // the scan staging and downsample buffers are shared with the pipeline
-  if (n > ctx->cap.max_points_per_scan) {
-    ctx->err = "vg_lio_kdtree: scan larger than max_points_per_scan";
-    return VG_E_CAPACITY;
-  }
-  *valid = -1;
-  *iters = 0;
-  HX x_curr;
-  x_curr.t = state[0];
-  memcpy(x_curr.R.a, state + 1, 72);
-  memcpy(x_curr.p.a, state + 10, 24);
-  memcpy(x_curr.v.a, state + 13, 24);
-  memcpy(x_curr.bg.a, state + 16, 24);
-  memcpy(x_curr.ba.a, state + 19, 24);
-  memcpy(x_curr.g.a, state + 22, 24);
-  memcpy(x_curr.cov.a, state + 25, 225 * sizeof(double));
-  {
-    std::vector<float> soa((size_t)3 * n);
-    for (int i = 0; i < n; i++) {
-      soa[i] = xyz[3 * i];
-      soa[(size_t)n + i] = xyz[3 * i + 1];
-      soa[(size_t)2 * n + i] = xyz[3 * i + 2];
-    }
-    VG_HIP(hipMemcpy(ctx->d_x, soa.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    VG_HIP(hipMemcpy(ctx->d_y, soa.data() + n, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    VG_HIP(hipMemcpy(ctx->d_z, soa.data() + 2 * (size_t)n, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (n == 0) return VG_OK;
-  VG_TRY(kd_lio(ctx, n, x_curr, valid, iters));
-  state_out(x_curr, state);
-  return VG_OK;
-}
-
-// the kd-tree IEKF on the scan in ctx->d_x/y/z (n points, raw LiDAR frame);
-// x_curr in/out; the map is extended with the scan at the result
-int kd_lio(vg_ctx* ctx, int n, HX& x_curr, int* valid, int* iters) {
-  *valid = -1;
-  *iters = 0;
-  if (ctx->kd.n < 100) {  // 275-310: seed the map with the scan at the current pose
-    VG_TRY(kd_update(ctx, n, x_curr.R.a, x_curr.p.a, false));
-    return VG_OK;
-  }
-  const int num_max_iter = 4;
-  const HX x_prop = x_curr;
-  bool flg_conv = false;
-  int rematch_num = 0;
-  M15 G = M15::Z(), cov_inv = inverse(x_curr.cov);
-  bool refind = true;
-  for (int it = 0; it < num_max_iter; it++) {
-    (*iters)++;
-    double sums[28];
-    VG_TRY(kd_pass(ctx, n, x_curr.R.a, x_curr.p.a, refind ? 1 : 0, sums));
-    M15 HTH15 = M15::Z();
-    double HTz[6];
-    int k = 0;
-    for (int r = 0; r < 6; r++)
-      for (int c = r; c < 6; c++, k++) HTH15(r, c) = HTH15(c, r) = sums[k];
-    for (int r = 0; r < 6; r++) HTz[r] = sums[21 + r];
-    *valid = (int)sums[27];
-    M15 Kin;  // H_T_H + cov_inv / 1000 (odometry.cpp:393)
-    for (int r = 0; r < 15; r++)
-      for (int c = 0; c < 15; c++) Kin(r, c) = HTH15(r, c) + cov_inv(r, c) / 1000;
-    const M15 K_1 = inverse(Kin);
-    for (int r = 0; r < 15; r++)  // G(:, 0:6) = K_1(:, 0:6) HTH
-      for (int c = 0; c < 6; c++) {
-        double g = 0.0;
-        for (int q = 0; q < 6; q++) g += K_1(r, q) * HTH15(q, c);
-        G(r, c) = g;
-      }
-    const V15 vec = x_prop.minus(x_curr);
-    V15 sol;
-    for (int r = 0; r < 15; r++) {  // K_1(:,0:6) HTz + vec - G(:,0:6) vec(0:6)
-      double a = 0.0, b = 0.0;
-      for (int q = 0; q < 6; q++) a += K_1(r, q) * HTz[q];
-      for (int q = 0; q < 6; q++) b += G(r, q) * vec[q];
-      sol[r] = (a + vec[r]) - b;
-    }
-    x_curr.plus(sol);
-    const double rn = sqrt((sol[0] * sol[0] + sol[1] * sol[1]) + sol[2] * sol[2]);
-    const double tn = sqrt((sol[3] * sol[3] + sol[4] * sol[4]) + sol[5] * sol[5]);
-    refind = false;
-    if ((rn * 57.3 < 0.01) && (tn * 100 < 0.015)) {
-      refind = true;
-      flg_conv = true;
-      rematch_num++;
-    }
-    if (it == num_max_iter - 2 && !flg_conv) refind = true;
-    if (rematch_num >= 2 || it == num_max_iter - 1) {  // cov = (I - G) cov
-      M15 nc;
-      for (int r = 0; r < 15; r++)
-        for (int c = 0; c < 15; c++) {
-          double a = 0.0;
-          for (int q = 0; q < 15; q++) a += ((r == q ? 1.0 : 0.0) - G(r, q)) * x_curr.cov(q, c);
-          nc(r, c) = a;
-        }
-      x_curr.cov = nc;
-      break;
-    }
-  }
-  VG_TRY(kd_update(ctx, n, x_curr.R.a, x_curr.p.a, true));  // 427-437
-  return VG_OK;
-}
-
-// x_curr now: between scans the absorbed host mirror; inside a scan (e.g.
-// save_pose_tum right after VNC_lio, local_mapping.cpp:429) the device state
-int host_state(vg_ctx* ctx, double* s) {
-  HostPipe* P = hp(ctx);
-  if (!P->in_scan) {
-    VG_TRY(host_sync(ctx));
-    state_out(P->x_curr, s);
-    return VG_OK;
-  }
-  VG_TRY(flush_deferred(ctx, P));
-  double* h = ctx->h_stage;
-  VG_HIP(hipMemcpyAsync(h, ctx->st->xc, kXC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  VG_HIP(stream_wait(ctx));
-  s[0] = P->cur.t;
-  memcpy(s + 1, h, kXS * sizeof(double));  // R, p, v, bg, ba, g
-  memcpy(s + 25, h + kXS, 225 * sizeof(double));
-  return VG_OK;
-}
-int host_window(vg_ctx* ctx, double* out) {
-  HostPipe* P = hp(ctx);
-  for (size_t i = 0; i < P->x_buf.size(); i++) state_out(P->x_buf[i], out + 250 * i);
-  return (int)P->x_buf.size();
-}
-int host_traj(vg_ctx* ctx, double* out, int cap, int from) {
-  HostPipe* P = hp(ctx);
-  int n = (int)P->traj.size() / kTrajRow;
-  const int k = from < n ? (n - from < cap ? n - from : cap) : 0;
-  if (out && k > 0) memcpy(out, P->traj.data() + (size_t)from * kTrajRow, (size_t)k * kTrajRow * sizeof(double));
-  return n;
-}
-int host_path(vg_ctx* ctx, double* out, int cap) {
-  HostPipe* P = hp(ctx);
-  int n = (int)P->path.size() / kPathRow;
-  if (out) memcpy(out, P->path.data(), (size_t)(n < cap ? n : cap) * kPathRow * sizeof(double));
-  return n;
-}
-int host_poll(vg_ctx* ctx) {
-  HostPipe* P = hp(ctx);
-  if (P->in_scan) return VG_OK;  // a stage-level scan is open: nothing to absorb mid-scan
-  return absorb_ready(ctx, P);
-}
-int host_stats_log(vg_ctx* ctx, vg_stats* out, int cap) {
-  HostPipe* P = hp(ctx);
-  int n = (int)P->stats_log.size();
-  if (out)
-    for (int i = 0; i < n && i < cap; i++) out[i] = P->stats_log[i];
-  return n;
-}
-
-// ---- checkpoint (checkpoint.hip): the host mirror's part, one byte blob.
-// Saved: what the next scan reads of HostPipe (the pending queue is empty and
-// no LM is outstanding after host_sync). Not saved: publication numbers and
-// everything per-scan; stats_log restarts at the load.
-int host_ckpt_allowed(vg_ctx* ctx, const char* who, bool save) {
-  HostPipe* P = hp(ctx);
-  const char* why = P->in_scan ? "a stage-level scan is open (vg_step_end first)"
-                    : save && init_active(P) ? "the cold-start initialisation is still running (until init_phase 3)"
-                    : ctx->shard.world > 1 ? "the context is sharded (world > 1)"
-                                           : nullptr;
-  if (!why) return save ? P->sticky : VG_OK;
-  ctx->err = std::string(who) + ": " + why;
-  return VG_E_STATE;
-}
-
-struct HostSnap {
-  HX x_curr;
-  std::vector<HX> x_buf;
-  std::vector<std::vector<double>> recs;  // imu_pre: bg, ba, then the device record
-  std::vector<int> mp;
-  int win_count = 0, win_base = 0, epoch = 0, release_flag = 0, first = 0;
-  double jour = 0, last_pcl_end_time = 0, sg = 1, last_pos[3] = {0, 0, 0};
-  int wp_n[32] = {0};
-  std::vector<double> traj, path;
-  vg_stats stats;
-};
-
-void host_ckpt_blob(vg_ctx* ctx, std::vector<unsigned char>& out) {
-  HostPipe* P = hp(ctx);
-  BlobW w{out};
-  double s[250];
-  state_out(P->x_curr, s);
-  w.f64s(s, 250);
-  w.i64((int64_t)P->x_buf.size());
-  for (const HX& x : P->x_buf) {
-    state_out(x, s);
-    w.f64s(s, 250);
-  }
-  w.i64((int64_t)P->imu_pre.size());
-  for (const HImuPre& q : P->imu_pre) {
-    w.f64s(q.bg.a, 3);
-    w.f64s(q.ba.a, 3);
-    std::vector<double> rec(kBaImuRec, 0.0);
-    if (q.rec.size() == (size_t)kBaImuRec) rec = q.rec;
-    else q.record(rec.data());
-    w.f64s(rec.data(), kBaImuRec);
-  }
-  w.i64((int64_t)P->mp.size());
-  for (int v : P->mp) w.i64(v);
-  w.i64(P->win_count);
-  w.i64(P->win_base);
-  w.i64(P->epoch);
-  w.i64(P->release_flag ? 1 : 0);
-  w.i64(P->first ? 1 : 0);
-  w.f64(P->jour);
-  w.f64(P->last_pcl_end_time);
-  w.f64(P->sg);
-  w.f64s(P->last_pos.a, 3);
-  for (int i = 0; i < 32; i++) w.i64(P->wp_n[i]);
-  w.i64((int64_t)P->traj.size());
-  w.f64s(P->traj.data(), P->traj.size());
-  w.i64((int64_t)P->path.size());
-  w.f64s(P->path.data(), P->path.size());
-  w.i64((int64_t)sizeof(vg_stats));
-  w.raw(&ctx->stats, sizeof(vg_stats));
-}
-
-static void state_in(HX& x, const double* s) {
-  x.t = s[0];
-  memcpy(x.R.a, s + 1, 72);
-  memcpy(x.p.a, s + 10, 24);
-  memcpy(x.v.a, s + 13, 24);
-  memcpy(x.bg.a, s + 16, 24);
-  memcpy(x.ba.a, s + 19, 24);
-  memcpy(x.g.a, s + 22, 24);
-  memcpy(x.cov.a, s + 25, 225 * sizeof(double));
-}
-
-int host_ckpt_parse(vg_ctx* ctx, const unsigned char* p, size_t n, void** snap) {
-  *snap = nullptr;
-  HostSnap* S = new HostSnap();
-  BlobR r{p, n};
-  double s[250];
-  const int W = ctx->cfg.win_size;
-  r.raw(s, sizeof(s));
-  if (r.ok) state_in(S->x_curr, s);
-  const size_t nb = r.count(sizeof(s), 32);
-  for (size_t i = 0; i < nb && r.ok; i++) {
-    r.raw(s, sizeof(s));
-    S->x_buf.emplace_back();
-    state_in(S->x_buf.back(), s);
-  }
-  const size_t ni = r.count((6 + kBaImuRec) * 8, 32);
-  for (size_t i = 0; i < ni && r.ok; i++) {
-    S->recs.emplace_back(6 + kBaImuRec);
-    r.raw(S->recs.back().data(), (6 + kBaImuRec) * 8);
-  }
-  const size_t nm = r.count(8, 32);
-  for (size_t i = 0; i < nm && r.ok; i++) S->mp.push_back((int)r.i64());
-  S->win_count = (int)r.i64();
-  S->win_base = (int)r.i64();
-  S->epoch = (int)r.i64();
-  S->release_flag = (int)r.i64();
-  S->first = (int)r.i64();
-  S->jour = r.f64();
-  S->last_pcl_end_time = r.f64();
-  S->sg = r.f64();
-  r.raw(S->last_pos, 24);
-  for (int i = 0; i < 32; i++) S->wp_n[i] = (int)r.i64();
-  const size_t nt = r.count(8, (size_t)1 << 40);
-  S->traj.resize(r.ok ? nt : 0);
-  r.raw(S->traj.data(), nt * 8);
-  const size_t np = r.count(8, (size_t)1 << 40);
-  S->path.resize(r.ok ? np : 0);
-  r.raw(S->path.data(), np * 8);
-  const size_t ns = r.count(1, sizeof(vg_stats));
-  memset(&S->stats, 0, sizeof(vg_stats));
-  r.raw(&S->stats, ns);
-  bool good = r.ok && r.at == n && ns == sizeof(vg_stats) && (int)nm == W && S->win_count >= 0 && S->win_count <= W &&
-              (int)nb == S->win_count && ni == (nb > 0 ? nb - 1 : 0) && nt % kTrajRow == 0 && np % kPathRow == 0 &&
-              S->win_base >= 0 && S->epoch >= 0;
-  for (size_t i = 0; good && i < nm; i++) good = S->mp[i] >= 0 && S->mp[i] < W;
-  for (int i = 0; good && i < 32; i++) good = S->wp_n[i] >= 0 && S->wp_n[i] <= ctx->cap.max_points_per_scan;
-  if (!good) {
-    delete S;
-    return VG_E_ARG;
-  }
-  *snap = S;
-  return VG_OK;
-}
-
-void host_ckpt_drop(void* snap) { delete (HostSnap*)snap; }
-
-// after vg_reset: HostPipe is fresh (host_init)
-void host_ckpt_install(vg_ctx* ctx, void* snap) {
-  HostSnap* S = (HostSnap*)snap;
-  HostPipe* P = hp(ctx);
-  P->x_curr = S->x_curr;
-  P->x_buf = S->x_buf;
-  P->imu_pre.clear();
-  for (const std::vector<double>& q : S->recs) {
-    P->imu_pre.emplace_back(v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]));
-    P->imu_pre.back().rec.assign(q.begin() + 6, q.end());
-  }
-  P->mp = S->mp;
-  P->win_count = S->win_count;
-  P->win_base = S->win_base;
-  P->epoch = S->epoch;
-  P->release_flag = S->release_flag != 0;
-  P->first = S->first != 0;
-  P->jour = S->jour;
-  P->last_pcl_end_time = S->last_pcl_end_time;
-  P->sg = S->sg;
-  memcpy(P->last_pos.a, S->last_pos, 24);
-  memcpy(P->wp_n, S->wp_n, sizeof(P->wp_n));
-  P->traj.swap(S->traj);
-  P->path.swap(S->path);
-  ctx->stats = S->stats;
-  if (P->init) init_finish(P->init);  // a saved context is past its cold start (host_ckpt_allowed)
-  delete S;
+  return step_tail(ctx, imu, m);
 }
 
 }  // namespace vg

@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) k_scan_begin(XcArg xa, DState* __restrict
 }
 
 // IMUEKF::process's state / covariance propagation (imu_ekf.cpp:13-86, the
-// host's propagate() in pipeline.cpp, same expression trees) from the device's
+// host's propagate() in imu_prop.cpp, same expression trees) from the device's
 // x_curr, then the scan opening (k_scan_begin). One workgroup: the per-sample
 // rotations (Exp, the sin / cos) in parallel, the rotation / velocity /
 // position chain on one lane in registers (inputs loaded a step ahead), the F

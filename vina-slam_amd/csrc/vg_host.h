@@ -1,7 +1,8 @@
 // vg_host.h — host-side pipeline state shared by pipeline.cpp (the
-// steady-state loop) and init.cpp (the cold-start initialisation, SURVEY row
-// f2): the host mirror of the estimator state, the IMU preintegration, the
-// pending-publication queue.
+// steady-state loop), host_mirror.cpp (the mirror's absorption and accessors),
+// imu_prop.cpp, kdlio_host.cpp, ckpt_host.cpp and init.cpp (the cold-start
+// initialisation): the host mirror of the estimator state and
+// its flat layouts, the IMU preintegration, the pending-publication queue.
 #pragma once
 #include <deque>
 #include <functional>
@@ -41,6 +42,46 @@ struct HX {  // IMUST (types.hpp:43-113)
     return a;
   }
 };
+
+// HX <-> flat doubles: the one packing ladder per direction, and the layouts
+// built on it
+//   frame (kXS):    R 9, p 3, v 3, bg 3, ba 3, g 3
+//   block (kXC):    frame, cov 15x15 row-major   (DState::xc, Pub::xc, begin_xc)
+//   state (kState): t, block                     (vg_seed / vg_get_state / the checkpoint blob)
+constexpr int kState = 1 + kXC;
+static_assert(kXS == 9 + 5 * 3 && kXC == kXS + 225 && kState == 250, "HX layouts");
+static inline void hx_put_frame(const HX& x, double* o) {
+  memcpy(o, x.R.a, 72);
+  memcpy(o + 9, x.p.a, 24);
+  memcpy(o + 12, x.v.a, 24);
+  memcpy(o + 15, x.bg.a, 24);
+  memcpy(o + 18, x.ba.a, 24);
+  memcpy(o + 21, x.g.a, 24);
+}
+static inline void hx_get_frame(HX& x, const double* o) {
+  memcpy(x.R.a, o, 72);
+  memcpy(x.p.a, o + 9, 24);
+  memcpy(x.v.a, o + 12, 24);
+  memcpy(x.bg.a, o + 15, 24);
+  memcpy(x.ba.a, o + 18, 24);
+  memcpy(x.g.a, o + 21, 24);
+}
+static inline void hx_put_block(const HX& x, double* o) {
+  hx_put_frame(x, o);
+  memcpy(o + kXS, x.cov.a, 225 * sizeof(double));
+}
+static inline void hx_get_block(HX& x, const double* o) {
+  hx_get_frame(x, o);
+  memcpy(x.cov.a, o + kXS, 225 * sizeof(double));
+}
+static inline void hx_put_state(const HX& x, double* s) {
+  s[0] = x.t;
+  hx_put_block(x, s + 1);
+}
+static inline void hx_get_state(HX& x, const double* s) {
+  x.t = s[0];
+  hx_get_block(x, s + 1);
+}
 
 struct Imu {
   double t;
@@ -218,8 +259,14 @@ static inline std::vector<Imu> to_imus(const double* imu, int m) {
 }
 
 // pipeline.cpp
+int flush_deferred(vg_ctx* ctx, HostPipe* P);  // the deferred scan opening and window push, on their own
+// imu_prop.cpp
 void propagate(vg_ctx* ctx, HostPipe* P, const std::vector<Imu>& imus, double pcl_beg, double pcl_end);
+// host_mirror.cpp
 int absorb(vg_ctx* ctx, HostPipe* P, bool full);
+int resolve_lm(vg_ctx* ctx, HostPipe* P, bool block = true);  // the pending LM's outcome (stage_ba left it)
+int degenerate_of(const double* nnt);                        // LioStateEstimation's return value from sum n n^T
+// kdlio_host.cpp
 int kd_lio(vg_ctx* ctx, int n, HX& x_curr, int* valid, int* iters);  // on the scan in ctx->d_x/y/z
 // init.cpp
 InitState* init_create(vg_ctx* ctx);

@@ -231,7 +231,7 @@ struct BaBufs {
 // ---- device-resident estimator state (state.hip) ----
 // The per-scan state lives in HBM for the whole scan: the IEKF update, the
 // window push, the BA and the slide all read and write it on the device, so
-// the host never waits for an intermediate result. The host mirror (pipeline.cpp)
+// the host never waits for an intermediate result. The host mirror (host_mirror.cpp)
 // is refreshed from the host-mapped publication block below.
 constexpr int kXS = 24;             // per-frame state: R 9, p 3, v 3, bg 3, ba 3, g 3
 constexpr int kXC = kXS + 225;      // x_curr: frame state + cov 15x15 (row-major)
@@ -503,7 +503,7 @@ struct vg_ctx {
   hipEvent_t in_ev = nullptr;  // the current scan's unpack (the split IEKF stream waits for it)
 
   vg_stats stats;
-  void* host = nullptr;     // host-side pipeline state (pipeline.cpp)
+  void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
   // stage timing with HIP events on the context stream (vg_profile)
   bool prof_on = false;      // k_iekf launch events (vg_profile bit 0)
   int prof_every = 0;        // sample k_ba_solve events on every n-th BA run (vg_profile bits 8-15)
@@ -805,7 +805,8 @@ const int* ba_hess_dev(vg_ctx* ctx);  // Hessian passes of the last LM run (I_H 
 int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_ring, double* out);
 int ba_factor_normals(vg_ctx* ctx, std::vector<double>& normals);
 int ba_solve_test(vg_ctx* ctx, const double* A, const double* b, double* x);  // vgx_ba_solve  // column 0 of each factor's eigenvectors
-// pipeline.cpp
+// host_mirror.cpp: the host mirror's lifetime, absorption and accessors
+// (host_sync, host_stats_log below as well)
 void host_init(vg_ctx* ctx);
 void host_free(vg_ctx* ctx);
 void host_reset(vg_ctx* ctx);
@@ -815,9 +816,11 @@ int host_window(vg_ctx* ctx, double* out);
 int host_traj(vg_ctx* ctx, double* out, int cap, int from = 0);  // rows [from, from + cap), returns the row count
 int host_path(vg_ctx* ctx, double* out, int cap);
 int host_poll(vg_ctx* ctx);
+int host_win_count(vg_ctx* ctx);
+// pipeline.cpp: the per-scan loop (host_step_deskew, the stage_* entry points,
+// host_quiesce and host_release_* below as well)
 int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, int n, double beg,
               double end, const double* imu, int m);
-int host_win_count(vg_ctx* ctx);
 int host_memo_probe(vg_ctx* ctx, int* out);  // map_memo_probe with the context's map parameters
 int iekf_update_test(vg_ctx* ctx, int nb, const double* partials, int n_points, const double* x_curr,
                      const double* x_prop, int it, int rematch, double* x_out, double* G6_out,
@@ -847,7 +850,7 @@ int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, lo
 int map_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, int* nodes, int* nfix, int cap, int* count);
 // the root hash rebuilt from (key, id) pairs filed by id, by the bidding rounds (lifetime.hip)
 int map_hash_place(vg_ctx* ctx, int nl, long nroots, const uint64_t* rkey, int* pos, int* rcnt, const char* who);
-// checkpoint.hip / pipeline.cpp: the host mirror's part of a checkpoint (a byte
+// checkpoint.hip / ckpt_host.cpp: the host mirror's part of a checkpoint (a byte
 // blob, one section of the file). host_ckpt_parse only reads: it fills an
 // opaque snapshot that host_ckpt_install puts in place after the reset
 // (host_ckpt_drop frees one that was not installed)
@@ -865,7 +868,7 @@ int markers_read(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferr
 int map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n);
 void markers_free(vg_ctx* ctx);
 int host_quiesce(vg_ctx* ctx);  // host_sync between scans; inside an open scan the context stream's drain
-int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters);
+int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters);  // kdlio_host.cpp
 int decode_scan(vg_ctx* ctx, const void* records, int n, const vg_lidar_format* fmt, float* xyz, float* inten,
                 float* time, int* n_out);  // decode.hip
 int host_stats_log(vg_ctx* ctx, vg_stats* out, int cap);

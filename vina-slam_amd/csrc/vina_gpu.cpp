@@ -539,13 +539,21 @@ static int upload_done(vg_ctx* ctx, int slot, int r) {
   return r;
 }
 
-int vg_step(vg_ctx* ctx, const float* xyz, const float* intensity, int n, double pcl_beg_time,
-            double pcl_end_time, const double* imu, int m) {
-  if (!ctx || (!xyz && n > 0) || n < 0 || m < 0 || (m > 0 && !imu)) return VG_E_ARG;
+// what the four vg_step* entry points check alike, behind their own pointer
+// checks (an argument error comes before a capacity error)
+static int check_scan(vg_ctx* ctx, int n, int m, const double* imu) {
+  if (!ctx || n < 0 || m < 0 || (m > 0 && !imu)) return VG_E_ARG;
   if (n > ctx->cap.max_points_per_scan) {
     ctx->err = "scan larger than max_points_per_scan";
     return VG_E_CAPACITY;
   }
+  return VG_OK;
+}
+
+int vg_step(vg_ctx* ctx, const float* xyz, const float* intensity, int n, double pcl_beg_time,
+            double pcl_end_time, const double* imu, int m) {
+  if (n > 0 && !xyz) return VG_E_ARG;
+  VG_TRY(check_scan(ctx, n, m, imu));
   if (n == 0) return host_step(ctx, ctx->d_x, ctx->d_y, ctx->d_z, ctx->d_i, n, pcl_beg_time, pcl_end_time, imu, m);
   float* p[5];
   int slot = 0;
@@ -555,32 +563,23 @@ int vg_step(vg_ctx* ctx, const float* xyz, const float* intensity, int n, double
 
 int vg_step_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, const float* d_intensity, int n,
                 double pcl_beg_time, double pcl_end_time, const double* imu, int m) {
-  if (!ctx || n < 0 || m < 0 || (m > 0 && !imu) || (n > 0 && (!d_x || !d_y || !d_z))) return VG_E_ARG;
-  if (n > ctx->cap.max_points_per_scan) {
-    ctx->err = "scan larger than max_points_per_scan";
-    return VG_E_CAPACITY;
-  }
+  if (n > 0 && (!d_x || !d_y || !d_z)) return VG_E_ARG;
+  VG_TRY(check_scan(ctx, n, m, imu));
   return host_step(ctx, d_x, d_y, d_z, d_intensity, n, pcl_beg_time, pcl_end_time, imu, m);
 }
 
 int vg_step_deskew_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, const float* d_intensity,
                        const float* d_time, int n, double pcl_beg_time, double pcl_end_time, const double* imu,
                        int m) {
-  if (!ctx || n < 0 || m < 0 || (m > 0 && !imu) || (n > 0 && (!d_x || !d_y || !d_z || !d_time))) return VG_E_ARG;
-  if (n > ctx->cap.max_points_per_scan) {
-    ctx->err = "scan larger than max_points_per_scan";
-    return VG_E_CAPACITY;
-  }
+  if (n > 0 && (!d_x || !d_y || !d_z || !d_time)) return VG_E_ARG;
+  VG_TRY(check_scan(ctx, n, m, imu));
   return host_step_deskew(ctx, d_x, d_y, d_z, d_intensity, d_time, n, pcl_beg_time, pcl_end_time, imu, m);
 }
 
 int vg_step_deskew(vg_ctx* ctx, const float* xyz, const float* intensity, const float* time, int n,
                    double pcl_beg_time, double pcl_end_time, const double* imu, int m) {
-  if (!ctx || (n > 0 && (!xyz || !time)) || n < 0 || m < 0 || (m > 0 && !imu)) return VG_E_ARG;
-  if (n > ctx->cap.max_points_per_scan) {
-    ctx->err = "scan larger than max_points_per_scan";
-    return VG_E_CAPACITY;
-  }
+  if (n > 0 && (!xyz || !time)) return VG_E_ARG;
+  VG_TRY(check_scan(ctx, n, m, imu));
   if (n == 0)
     return host_step_deskew(ctx, ctx->d_x, ctx->d_y, ctx->d_z, ctx->d_i, ctx->d_t, n, pcl_beg_time, pcl_end_time, imu,
                             m);
