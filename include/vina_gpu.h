@@ -293,6 +293,104 @@ int vg_release_far(vg_ctx* ctx, int flags, long long* out);
  * policy, vg_profile; vg_stats_log restarts at the load. */
 int vg_checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes);
 int vg_checkpoint_load(vg_ctx* ctx, const char* path);
+
+/* ---- Localising in a saved map --------------------------------------------
+ * Frozen-map (localisation) mode. on = 1 (the default): vg_step* maps as
+ * before. on = 0: the map is read-only. A scan with mapping off runs the
+ * propagation (and the deskew where per-point times are given), the
+ * downsample with its /2 fallback and the IEKF; x_curr becomes the IEKF
+ * result and the scan ends: one TUM row, one path row (carrying the last value
+ * of jour), the per-scan stats (n_raw, n_ds, iekf_*, degenerate as usual;
+ * roots_new, n_slide, n_factors, ba_iters, plane_updates, fix_full and v_ins
+ * 0; nodes_used and fix_used unchanged). No window push, insert, recut, LM,
+ * margi or slide: the node pool, the point_fix arena, the root hash, the slide
+ * list, the window arrays and win_count stay bit for bit what they were.
+ * The switch completes the outstanding work first. Between scans only:
+ * VG_E_STATE inside an open stage-level scan, before a cold start has reached
+ * init_phase 3, and on a sharded context with world > 1.
+ * With mapping off the stage-level API allows vg_scan_load / vg_scan_bind_dev,
+ * vg_propagate, vg_downsample_scan, vg_lio_state_estimation and vg_step_end;
+ * vg_window_push, vg_cut_voxel_multi, vg_multi_recut, vg_damping_iter and
+ * vg_multi_margi return VG_E_STATE (the open scan stays usable).
+ * vg_release_far erases nothing and returns out[0] = -1 (the census of flags
+ * bit 1 still works); vg_checkpoint_save works; the mode is not part of a
+ * checkpoint, and a load keeps the loading context's mode; vg_set_publish
+ * bit 1 emits no markers. Turning mapping back on continues the saved session
+ * from the frozen window. */
+int vg_set_mapping(vg_ctx* ctx, int on);
+
+/* Pose-hypothesis scoring: OctoTree::match (octree.cpp:551-595,
+ * voxel_map.cpp:241-266) for one scan under K candidate poses in one
+ * dispatch. Reads the map only. */
+typedef struct vg_pose_score {   /* 80 bytes, no implicit padding */
+  int32_t matches;               /* points for which match() returned 1 */
+  int32_t in_map;                /* points whose root voxel exists and whose descent reached a leaf */
+  double  cost;                  /* sum r^2 / (0.0005 + sigma_d) over the matches */
+  double  sum_abs;               /* sum |r| over the matches */
+  double  nn[6];                 /* sum n n^T, upper triangle (xx xy xz yy yz zz): the IEKF's degeneracy input */
+  double  reserved;
+} vg_pose_score;
+/* per_point record of vg_score_poses (24 bytes) */
+typedef struct vg_point_match {
+  int32_t leaf;                  /* node id of the leaf the descent reached, -1: none */
+  int32_t flag;                  /* match() returned 1 */
+  double  r;                     /* n . (w - c), signed; 0 where flag = 0 */
+  double  sigma_d;               /* the gate's variance; 0 where flag = 0 */
+} vg_point_match;
+#define VG_SCORE_MAX_POSES 65536
+/* xyz: n x 3 floats, LiDAR frame (what the IEKF reads; vg_scan_points' or
+ *   vg_downsample's output for a downsampled cloud); var_init as the IEKF
+ *   applies it (extrinsic, calcBodyVar).
+ * poses: K x 12 doubles [R row-major 9, p 3], IMU in world (state[1..12]).
+ * pose_var: 18 doubles [rot_var 3x3, tsl_var 3x3] shared by all K, or NULL for
+ *   zero: the two blocks the IEKF takes from the state covariance.
+ * per_point (may be NULL; K must be 1): n vg_point_match records.
+ * The sums are deterministic and independent of K: a pose's record has the
+ * same bits scored alone or at any position of any batch. n == 0 or an empty
+ * map gives all-zero records; a point whose voxel key is out of the packed
+ * range (|key| >= 2^20) counts as not in the map. K <= 0, K >
+ * VG_SCORE_MAX_POSES, n < 0, n > max_points_per_scan or a NULL pointer:
+ * VG_E_ARG. Completes outstanding work first; between scans or inside an open
+ * stage-level scan; works in either mode. Unsharded contexts only. */
+int vg_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, int K,
+                   const double* pose_var, vg_pose_score* out, void* per_point);
+
+/* Relocalise: recover the pose of a scan in the map from a rough guess. A
+ * grid of hypotheses around the guess is scored in one vg_score_poses
+ * dispatch and ranked by matches, then by lower cost / matches; the best
+ * refine_top are refined by LiDAR-only Gauss-Newton on the 6 pose unknowns
+ * against the frozen map (the IEKF's own 6 x 6 normal equations, no prior,
+ * solved on the host in double, one launch per iteration); the winner is the
+ * best refined score. */
+typedef struct vg_reloc_params {
+  double half_xy, step_xy;       /* search window and step in x and y around the guess, metres */
+  double half_z,  step_z;        /* 0 / 0: keep the guess's z */
+  double half_yaw, step_yaw;     /* about the gravity direction of the context's state, radians */
+  int    refine_top;             /* best coarse hypotheses refined (<= 0: 8) */
+  int    refine_iters;           /* Gauss-Newton iterations each (<= 0: 8) */
+  double min_match_ratio;        /* success: matches / n of the refined winner (<= 0: 0.5) */
+  double reserved[4];
+} vg_reloc_params;
+/* The hypothesis grid of vg_relocalize, without a device: per axis the offsets
+ * i * step for |i| <= floor(half / step) (one value, 0, where half or step is
+ * 0). Order: z outermost, then yaw, then the x-y plane in 4 x 4 patches (patch
+ * rows along y, patches and the cells inside each in row-major order, x
+ * fastest), so that 16 consecutive hypotheses, one workgroup's pose tile in
+ * vg_score_poses, are neighbours in the plane and touch the same root voxels.
+ * out (may be NULL): cap x 4 doubles [dx, dy, dz, dyaw]; *count = the grid's
+ * size. More than VG_SCORE_MAX_POSES hypotheses, a negative half or step:
+ * VG_E_ARG. */
+int vg_reloc_grid(const vg_reloc_params* prm, double* out, int cap, int* count);
+/* guess_pose, out_pose: 12 doubles [R 9, p 3]. out_score: the refined winner's
+ * record; *ok = 1 on success. install != 0 and success: x_curr takes the pose;
+ * v, bg, ba and g keep the context's values (v = 0 when the context has never
+ * stepped) and the covariance is reset to the initial covariance
+ * (imu_ekf.cpp: 1e-4 on rotation, position and velocity, 1e-5 on the biases).
+ * A failure (*ok = 0) returns VG_OK and leaves the context's state untouched.
+ * Completes outstanding work; between scans only (VG_E_STATE inside one). */
+int vg_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess_pose,
+                  const vg_reloc_params* prm, int install, double* out_pose, vg_pose_score* out_score, int* ok);
+
 /* Window states x_buf (win_count x 250 doubles); returns win_count via *n. */
 int vg_window_states(vg_ctx* ctx, double* out, int* n);
 

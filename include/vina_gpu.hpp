@@ -111,6 +111,21 @@ class LioCore {
     return bytes;
   }
   void load_checkpoint(const std::string& file) { check(vg_checkpoint_load(ctx_, file.c_str()), "vg_checkpoint_load"); }
+  // localising in a saved map: the frozen-map switch, pose scoring, relocalisation (vina_gpu.h)
+  void set_mapping(bool on) { check(vg_set_mapping(ctx_, on ? 1 : 0), "vg_set_mapping"); }
+  std::vector<vg_pose_score> score_poses(const float* xyz, int n, const double* poses, int K,
+                                         const double* pose_var = nullptr, vg_point_match* per_point = nullptr) {
+    std::vector<vg_pose_score> out((size_t)(K > 0 ? K : 0));
+    check(vg_score_poses(ctx_, xyz, n, poses, K, pose_var, out.data(), per_point), "vg_score_poses");
+    return out;
+  }
+  // returns ok; out_pose: 12 doubles [R, p]; score may be null
+  bool relocalize(const float* xyz, int n, const double* guess_pose, const vg_reloc_params& prm, bool install,
+                  double* out_pose, vg_pose_score* score) {
+    int ok = 0;
+    check(vg_relocalize(ctx_, xyz, n, guess_pose, &prm, install ? 1 : 0, out_pose, score, &ok), "vg_relocalize");
+    return ok != 0;
+  }
   void marker_capacity(int max_records) { check(vg_marker_capacity(ctx_, max_records), "vg_marker_capacity"); }
   std::vector<vg_plane_marker> markers(int* deferred = nullptr) {
     int n = 0, d = 0;

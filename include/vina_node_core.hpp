@@ -74,6 +74,13 @@ inline std::string tum_line(const PoseStamped& s) {
   return b;
 }
 
+// The node's localisation parameters (General.localization_mode,
+// General.map_path): with the defaults the node maps as before
+struct NodeParams {
+  int localization_mode = 0;  // 1: load map_path and run with the map frozen (vg_set_mapping 0)
+  std::string map_path;
+};
+
 class NodeCore {
  public:
   // cfg.cold_start = 1 for a run from a bag (the node's initialization,
@@ -141,6 +148,12 @@ class NodeCore {
         continue;
       }
       Scan& sc = it->second;
+      if (reloc_armed_) {  // the first scan after load_map: its pose in the map, from the guess
+        double pose[12];
+        reloc_ok_ = lio_.relocalize(sc.xyz.data(), (int)sc.inten.size(), reloc_guess_, reloc_prm_, true, pose, nullptr);
+        reloc_armed_ = false;
+        reloc_done_ = true;
+      }
       check(vg_step_deskew(lio_.raw(), sc.xyz.data(), sc.inten.data(), sc.time.data(), (int)sc.inten.size(), beg,
                            end, imu.data(), m),
             "vg_step_deskew");
@@ -186,6 +199,26 @@ class NodeCore {
     scans_done_ = -1;  // (take_rows: read everything again)
     finish();
   }
+  // Localisation in a saved map: load_map installs the checkpoint and turns
+  // mapping off; relocalize(guess, ...) arms a relocalisation (vg_relocalize,
+  // install = 1) on the first scan stepped after it, whose result
+  // relocalized() / relocalize_ok() report. apply(params) does the first for
+  // General.localization_mode = 1.
+  void load_map(const std::string& file) {
+    load_checkpoint(file);
+    lio_.set_mapping(false);
+  }
+  void apply(const NodeParams& p) {
+    if (p.localization_mode == 1) load_map(p.map_path);
+  }
+  void relocalize(const double guess_pose[12], const vg_reloc_params& prm) {
+    for (int k = 0; k < 12; k++) reloc_guess_[k] = guess_pose[k];
+    reloc_prm_ = prm;
+    reloc_armed_ = true;
+    reloc_done_ = false;
+  }
+  bool relocalized() const { return reloc_done_; }
+  bool relocalize_ok() const { return reloc_ok_; }
   void skip_packages(int n) { skip_ = n; }
   void set_package_limit(int n) { package_limit_ = n; }  // spin() returns once this many packages were taken (-1: no limit)
   int packages() const { return packages_; }             // packages sync_packages has delivered, skipped ones included
@@ -340,6 +373,9 @@ class NodeCore {
   int scans_done_ = 0;
   int packages_ = 0, skip_ = 0, package_limit_ = -1;
   std::vector<PoseStamped> tum_, path_;
+  bool reloc_armed_ = false, reloc_done_ = false, reloc_ok_ = false;
+  double reloc_guess_[12] = {};
+  vg_reloc_params reloc_prm_ = {};
   int publish_ = 0;  // vg_set_publish flags
   bool visualization_ = false;
   std::vector<vg_plane_marker> markers_, marker_buf_;

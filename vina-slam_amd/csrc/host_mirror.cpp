@@ -160,6 +160,10 @@ static int absorb_p2(vg_ctx* ctx, HostPipe* P, Pend& q) {
   }
   q.st.fix_full = c[kCntFixFull];
   q.st.v_ins = c[kCntSeg];
+  if (q.frozen) {  // the counters are the last mapping scan's: nothing of this scan touched the map
+    q.st.n_slide = q.st.roots_new = q.st.plane_updates = q.st.fix_full = q.st.v_ins = 0;
+    q.st.n_ds = q.n_ds;  // the downsample's own count (no insert took it)
+  }
   // events recorded while this scan was enqueued are complete now
   collect_iekf_events(ctx, q);
   for (int i = 0; i < kProfN; i++)

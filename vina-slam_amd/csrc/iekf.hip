@@ -4,7 +4,7 @@
 //   A7  match / OctoTree::match / inside  voxel_map.cpp:241-266, octree.cpp:551-595, 732-737
 //   A9  LioStateEstimation point loop     odometry.cpp:111-148
 #include <hipcub/hipcub.hpp>
-#include "vg_iekf.h"
+#include "vg_match.h"
 
 namespace vg {
 
@@ -14,103 +14,8 @@ namespace vg {
 // probabilistic point-to-plane gate (octree.cpp:557-579), the Jacobian and the
 // weighted normal-equation accumulation. Each block writes 34 partial sums:
 // HTH (upper 21), HTz (6), nnt (upper 6), match count (1). fp64 throughout.
-__device__ __forceinline__ int descend(const NodeHdr* __restrict__ hdr, int node, const V3& w) {
-  for (int d = 0; d < 8 && node >= 0; d++) {
-    const NodeHdr& h = hdr[node];
-    if (h.octo == 0) return node;
-    node = h.child[octant(w, h.center)];
-  }
-  return -1;
-}
-
-// OctoTree::match at a leaf; returns 1 and sigma on success
-__device__ __forceinline__ int match_leaf(const NodeHdr& h, const PlaneRec& P, const V3& wld, const M3& var_wld,
-                                          double& sigma) {
-  if (!h.is_plane) return 0;
-  V3 c = ld_v3(P.center), n = ld_v3(P.normal);
-  V3 d = sub(wld, c);
-  float dis_to_plane = fabs(dot3(n, d));
-  V3 cw = sub(c, wld);
-  float dis_to_center = cw[0] * cw[0] + cw[1] * cw[1] + cw[2] * cw[2];
-  float range_dis = (dis_to_center - dis_to_plane * dis_to_plane);
-  if (!(range_dis <= 3 * 3 * P.radius)) return 0;
-  double J[6] = {d[0], d[1], d[2], -n[0], -n[1], -n[2]};
-  double t[6];
-  for (int j = 0; j < 6; j++) {
-    double s = J[0] * P.var[sym_idx(6, 0, j)];
-    for (int k = 1; k < 6; k++) s += J[k] * P.var[sym_idx(6, k, j)];
-    t[j] = s;
-  }
-  double sl = t[0] * J[0];
-  for (int j = 1; j < 6; j++) sl += t[j] * J[j];
-  V3 vn = mul(var_wld, n);
-  sl += dot3(n, vn);
-  if (dis_to_plane < 3 * sqrt(sl)) {
-    sigma = sl;
-    return 1;
-  }
-  return 0;
-}
-
-__device__ __forceinline__ bool inside(const NodeHdr& h, const V3& w) {
-  double hl = h.qlen * 2;
-  return (w[0] >= h.center[0] - hl && w[0] <= h.center[0] + hl && w[1] >= h.center[1] - hl &&
-          w[1] <= h.center[1] + hl && w[2] >= h.center[2] - hl && w[2] <= h.center[2] + hl);
-}
-
-
-// ---- wave sums without LDS: the partner across lane bit L (lane ^ L) via
-// gfx950's v_permlane32_swap / v_permlane16_swap and DPP (row_ror:8, row
-// shifts by 4, quad perms)
-__device__ __forceinline__ double pack_d(unsigned lo, unsigned hi) {
-  return __longlong_as_double(((long long)hi << 32) | lo);
-}
-template <int C>
-__device__ __forceinline__ unsigned dpp32(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, C, 0xf, 0xf, false);
-}
-template <int L>
-__device__ __forceinline__ double xor_lane(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
-  if constexpr (L == 32) {  // r[0] = x[lane % 32], r[1] = x[lane % 32 + 32]
-    auto l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return (lane & 32) ? pack_d(l2[0], h2[0]) : pack_d(l2[1], h2[1]);
-  } else if constexpr (L == 16) {  // r[0] = the even row's x, r[1] = the odd row's
-    auto l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return (lane & 16) ? pack_d(l2[0], h2[0]) : pack_d(l2[1], h2[1]);
-  } else if constexpr (L == 8) {
-    return pack_d(dpp32<0x128>(lo), dpp32<0x128>(hi));  // row_ror:8
-  } else if constexpr (L == 4) {
-    const double up = pack_d(dpp32<0x104>(lo), dpp32<0x104>(hi));  // row_shl:4 (lane i <- i + 4)
-    const double dn = pack_d(dpp32<0x114>(lo), dpp32<0x114>(hi));  // row_shr:4 (lane i <- i - 4)
-    return (lane & 4) ? dn : up;
-  } else if constexpr (L == 2) {
-    return pack_d(dpp32<0x4E>(lo), dpp32<0x4E>(hi));  // quad_perm [2,3,0,1]
-  } else {
-    return pack_d(dpp32<0xB1>(lo), dpp32<0xB1>(hi));  // quad_perm [1,0,3,2]
-  }
-}
-// one level of a halving wave sum: the lanes with bit L clear keep the first
-// ceil(N/2) values, the others the rest, each adding its partner's copy
-template <int L, int N>
-__device__ __forceinline__ void halve(const double (&v)[N], double (&w)[(N + 1) / 2], int lane, int& idx, int& n) {
-  constexpr int H = (N + 1) / 2;
-  const bool hi = (lane & L) != 0;
-#pragma unroll
-  for (int j = 0; j < H; j++) {
-    const double a = v[j], b = (H + j < N) ? v[H + j] : 0.0;
-    w[j] = (hi ? b : a) + xor_lane<L>(hi ? a : b, lane);
-  }
-  if (hi) {
-    idx += H;
-    n = n > H ? n - H : 0;
-  } else {
-    n = n < H ? n : H;
-  }
-}
+// (descend, match_leaf, inside, the matched point's sums and the halving wave
+// sums: vg_match.h, shared with score.hip)
 
 // The pose (x_curr R, p and the rotation / translation covariance blocks) is
 // read from the device state the previous k_iekf_update wrote; the kernel is a
@@ -191,50 +96,10 @@ __device__ __forceinline__ void iekf_points(const MP& mp, const DState* __restri
     } else if (leaf == -1 && (it == 0 || cv < 0 || (cv & 0x40000000))) {
       cache[i] = -1;
     }
-    if (flag) {
-      const PlaneRec& P = m.pl[leaf];
-      V3 nn = ld_v3(P.normal), c = ld_v3(P.center);
-      double R_inv = 1.0 / (0.0005 + sigma);
-      double resi = dot3(nn, sub(wld, c));
-      V3 j3 = mul(mul(hat(pnt), Rt), nn);
-      double jac[6] = {j3[0], j3[1], j3[2], nn[0], nn[1], nn[2]};
-      int k = 0;
-      for (int r = 0; r < 6; r++) {
-        double jr_ = jac[r] * R_inv;
-        for (int c2 = r; c2 < 6; c2++, k++) acc[k] += jr_ * jac[c2];
-      }
-      for (int r = 0; r < 6; r++) acc[21 + r] -= jac[r] * (R_inv * resi);
-      acc[27] += nn[0] * nn[0];
-      acc[28] += nn[0] * nn[1];
-      acc[29] += nn[0] * nn[2];
-      acc[30] += nn[1] * nn[1];
-      acc[31] += nn[1] * nn[2];
-      acc[32] += nn[2] * nn[2];
-      acc[33] += 1.0;
-    }
+    if (flag) iekf_accum(acc, m.pl[leaf], pnt, Rt, wld, sigma);
   }
 }
-// the workgroup's 34 sums (threads < 34 hold one each): a halving butterfly
-// per wave, then LDS across the 4 waves (fixed tree). Every level pairs lane ^
-// L for L = 32, 16, ..., 1, so each sum is bit for bit lane 0's of a shfl_down
-// tree, but a lane hands over half of the values it carries at every level:
-// 37 exchanges for the 34 sums instead of 204, through permlane / DPP
-__device__ __forceinline__ double iekf_wg_sum(double (&acc)[kIekfVals], double (*red)[kIekfVals]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  static_assert(kIekfVals == 34, "the halving levels below are laid out for 34 sums");
-  int ridx = 0, rn = kIekfVals;
-  double h17[17], h9[9], h5[5], h3[3], h2[2], h1[1];
-  halve<32>(acc, h17, lane, ridx, rn);
-  halve<16>(h17, h9, lane, ridx, rn);
-  halve<8>(h9, h5, lane, ridx, rn);
-  halve<4>(h5, h3, lane, ridx, rn);
-  halve<2>(h3, h2, lane, ridx, rn);
-  halve<1>(h2, h1, lane, ridx, rn);
-  if (rn == 1) red[wv][ridx] = h1[0];
-  __syncthreads();
-  const int j = threadIdx.x < kIekfVals ? threadIdx.x : 0;
-  return ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-}
+// (iekf_wg_sum, the workgroup's 34 sums: vg_match.h)
 // the pose words an iteration's point loop reads from x_curr: R 9, p 3, the
 // rotation and translation covariance blocks 9 + 9
 __device__ __forceinline__ double pose_word(const double* xc, int t) {

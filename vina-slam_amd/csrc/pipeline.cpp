@@ -157,6 +157,13 @@ static int need_open(vg_ctx* ctx, HostPipe* P, const char* what) {
   return VG_OK;
 }
 
+// the map stages are refused while the map is frozen (vg_set_mapping); the open scan stays usable
+static int need_mapping(vg_ctx* ctx, const char* what) {
+  if (ctx->mapping) return VG_OK;
+  ctx->err = std::string(what) + ": mapping is off, the map is read-only (vg_set_mapping)";
+  return VG_E_STATE;
+}
+
 // the scan propagates on the device (k_scan_prop) rather than on the host
 // after a wait for the previous scan's state
 static bool prop_on_device(vg_ctx* ctx, const HostPipe* P, int m, bool dev) {
@@ -185,7 +192,7 @@ int stage_propagate(vg_ctx* ctx, const double* imu, int m, double beg, double en
   // it, behind the IEKF's enqueue); the first scan has nothing to propagate
   // A pending LM (the previous fused step returned before its outcome):
   // only the device has that scan's state, so it propagates there
-  P->begin_prop = prop_on_device(ctx, P, m, dev);
+  P->begin_prop = ctx->mapping && prop_on_device(ctx, P, m, dev);  // (a frozen scan: on the host, frozen_step)
   if (P->begin_prop) {
     PropArg& a = P->prop;
     const vg_config& c = ctx->cfg;
@@ -289,11 +296,13 @@ int stage_downsample(vg_ctx* ctx, const float* dx, const float* dy, const float*
   HostPipe* P = hp(ctx);
   VG_TRY(need_open(ctx, P, "vg_downsample_scan"));
   ds_adopt(P, dx, dy, dz, di, n);
-  P->ds_seq = n_ds_out ? ++ctx->pub_seq : -1;  // published only for a stage-level caller
-  VG_TRY(ds_enqueue_scan(ctx, dx, dy, dz, di, n, n_ds_out ? P->ds_seq : 0));
-  if (n_ds_out) {
+  // published only for a stage-level caller, and with the map frozen (no insert takes the count)
+  const bool pub = n_ds_out || !ctx->mapping;
+  P->ds_seq = pub ? ++ctx->pub_seq : -1;
+  VG_TRY(ds_enqueue_scan(ctx, dx, dy, dz, di, n, pub ? P->ds_seq : 0));
+  if (pub) {
     VG_TRY(resolve_ds(ctx, P));
-    *n_ds_out = P->ds_n;
+    if (n_ds_out) *n_ds_out = P->ds_n;
   }
   return VG_OK;
 }
@@ -319,6 +328,7 @@ int stage_iekf(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, i
 int stage_window_push(vg_ctx* ctx, const double* imu, int m) {
   HostTimer ht_(ctx, kHostPush);
   HostPipe* P = hp(ctx);
+  VG_TRY(need_mapping(ctx, "vg_window_push"));
   VG_TRY(need_open(ctx, P, "vg_window_push"));
   // the previous scan's window after its BA (the IMU_PRE bias below); already
   // absorbed unless this scan propagated on the device
@@ -362,6 +372,7 @@ int stage_insert(vg_ctx* ctx) {
   HostTimer ht_(ctx, kHostInsert);
   HostPipe* P = hp(ctx);
   const vg_config& c = ctx->cfg;
+  VG_TRY(need_mapping(ctx, "vg_cut_voxel_multi"));
   VG_TRY(need_open(ctx, P, "vg_cut_voxel_multi"));
   if (P->win_count <= 0) {
     ctx->err = "vg_map_insert: window is empty (push the scan first)";
@@ -525,6 +536,7 @@ int stage_recut(vg_ctx* ctx, int* nf_out) {
   HostTimer ht_(ctx, kHostRecut);
   HostPipe* P = hp(ctx);
   const vg_config& c = ctx->cfg;
+  VG_TRY(need_mapping(ctx, "vg_multi_recut"));
   VG_TRY(need_open(ctx, P, "vg_multi_recut"));
   VG_TRY(flush_deferred(ctx, P));
   const WinArg wa = make_winarg(P, 0);
@@ -561,6 +573,7 @@ int stage_ba(vg_ctx* ctx, int* iters_out, bool margi_follows) {
   HostTimer ht_(ctx, kHostBA);
   HostPipe* P = hp(ctx);
   const int W = ctx->cfg.win_size;
+  VG_TRY(need_mapping(ctx, "vg_damping_iter"));
   VG_TRY(need_open(ctx, P, "vg_damping_iter"));
   VG_TRY(flush_deferred(ctx, P));
   if (P->win_count < W) {
@@ -675,6 +688,7 @@ int stage_margi_slide(vg_ctx* ctx) {
   HostPipe* P = hp(ctx);
   const vg_config& c = ctx->cfg;
   const int W = c.win_size;
+  VG_TRY(need_mapping(ctx, "vg_multi_margi"));
   if (P->win_count < W) {
     ctx->err = "vg_margi: window not full";
     return VG_E_STATE;
@@ -720,6 +734,11 @@ int stage_finish(vg_ctx* ctx) {
   HostPipe* P = hp(ctx);
   VG_TRY(need_open(ctx, P, "vg_step_end"));
   VG_TRY(flush_deferred(ctx, P));
+  if (!ctx->mapping) {  // a frozen scan: x_curr is the IEKF's result; the main stream joins the downsample's
+    P->cur.frozen = true;
+    P->cur.n_ds = P->ds_n > 0 ? P->ds_n : 0;
+    if (P->ds_seq != 0) VG_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_ds_done, 0));
+  }
   if (!P->published) {
     P->cur.seq1 = ++ctx->pub_seq;
     VG_TRY(state_publish(ctx, P->win_count, nullptr, P->cur.seq1));
@@ -769,10 +788,12 @@ int host_release_far(vg_ctx* ctx, int flags, long long* out) {
     ctx->err = "vg_release_far: device jour " + std::to_string(dj) + " != host jour " + std::to_string(P->jour);
     return VG_E_STATE;
   }
-  const bool release = P->release_flag;
+  // with the map frozen nothing is erased or moved: the census alone (out[0] = -1); a pending release stays pending
+  const bool release = P->release_flag && ctx->mapping;
+  if (!ctx->mapping) flags &= ~1;
   const int thr = ctx->cfg.release_dis > 0 ? ctx->cfg.release_dis : 700;
   const int r = map_release(ctx, release, thr, P->jour, flags & 1, out);
-  if (r == VG_OK) P->release_flag = false;  // a failed release (e.g. its scratch allocation) stays pending
+  if (r == VG_OK && ctx->mapping) P->release_flag = false;  // a failed release (e.g. its scratch allocation) stays pending
   return r;
 }
 int host_memo_probe(vg_ctx* ctx, int* out) { return map_memo_probe(ctx, hp(ctx)->mpd, out); }
@@ -841,12 +862,34 @@ static int step_tail(vg_ctx* ctx, const double* imu, int m) {
   return stage_finish(ctx);
 }
 
+// One scan with mapping off (vg_set_mapping): the propagation on the host (it
+// absorbs the previous scan's published state; nothing else waits for it), the
+// deskew where per-point times are given, the IEKF on the main stream and the
+// downsample on its own, then the end of the scan. No launch here polls a
+// device flag: the IEKF is not split onto its stream (tail_a_valid and
+// sync_tail_armed were cleared by the switch, which also drained the last
+// mapping scan's margi tail, and only a margi sets them), the opening carries
+// no flag arguments, and the scan graph is never launched.
+static int frozen_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di,
+                       const float* dt, int n, double beg, double end, const double* imu, int m) {
+  VG_TRY(stage_propagate(ctx, imu, m, beg, end));
+  const float *x = dx, *y = dy, *z = dz, *i = di;
+  if (dt) {
+    VG_TRY(stage_deskew(ctx, dx, dy, dz, di, dt, n));
+    x = ctx->d_x, y = ctx->d_y, z = ctx->d_z, i = ctx->d_i;
+  }
+  VG_TRY(stage_iekf(ctx, x, y, z, n, nullptr));
+  VG_TRY(stage_downsample(ctx, x, y, z, i, n, nullptr));
+  return stage_finish(ctx);
+}
+
 // one scan with the deskew: the rest of the pipeline reads the staging
 // buffers. The propagation runs on the host (the deskew needs its IMU poses),
 // and the downsample follows the IEKF, on the deskewed scan
 int host_step_deskew(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di,
                      const float* dt, int n, double beg, double end, const double* imu, int m) {
   if (init_active(hp(ctx))) return init_step(ctx, dx, dy, dz, di, dt, n, beg, end, imu, m);
+  if (!ctx->mapping) return frozen_step(ctx, dx, dy, dz, di, dt, n, beg, end, imu, m);
   VG_TRY(stage_propagate(ctx, imu, m, beg, end));
   VG_TRY(stage_deskew(ctx, dx, dy, dz, di, dt, n));
   const float *x = ctx->d_x, *y = ctx->d_y, *z = ctx->d_z, *i = ctx->d_i;
@@ -859,6 +902,7 @@ int host_step_deskew(vg_ctx* ctx, const float* dx, const float* dy, const float*
 int host_step(vg_ctx* ctx, const float* dx, const float* dy, const float* dz, const float* di, int n, double beg,
               double end, const double* imu, int m) {
   if (init_active(hp(ctx))) return init_step(ctx, dx, dy, dz, di, nullptr, n, beg, end, imu, m);
+  if (!ctx->mapping) return frozen_step(ctx, dx, dy, dz, di, nullptr, n, beg, end, imu, m);
   // both read only the raw scan (local_mapping.cpp:396-413). The downsample
   // (its count stays on the device) goes first, on its own stream, before the
   // host waits for the previous scan's state: it runs under that scan's margi

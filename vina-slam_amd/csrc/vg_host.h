@@ -177,6 +177,8 @@ struct Pend {          // a scan whose device results the host has not absorbed 
   int ins_slot = -1;       // physical window slot its insert filled (wp_n once absorbed)
   int ev_base = 0, ev_n = 0;  // this scan's k_iekf event pairs (vg_profile)
   double t = 0;            // scan end time (trajectory row)
+  bool frozen = false;     // a scan with mapping off (vg_set_mapping): no map stage ran, its map counters read 0
+  int n_ds = 0;            // ... and its downsampled count, read from the downsample's publication
   bool init_tail = false;  // the scan motion_init succeeded on: its trajectory row and
                            // IEKF fields come from the initialisation (init.cpp)
   vg_stats st;

@@ -383,6 +383,18 @@ struct BaLoop {
   int seq0 = 0, enq = 0, tail_at = 0, k = 0;  // first iteration flag number, iterations enqueued, ahead of the tail, next k
   bool active = false;
 };
+// vg_score_poses / vg_relocalize scratch (score.hip): allocated on first use,
+// grown geometrically, freed by vg_destroy (score_free)
+struct ScoreBufs {
+  float* xyz = nullptr;       // the scored cloud, n x 3 as the caller gave it
+  double* poses = nullptr;    // K x 12
+  double* partials = nullptr; // [chunk][pose of the slab][kScoreVals], or [chunk][34] (the normal equations)
+  void* out = nullptr;        // K vg_pose_score records; the 34 reduced sums
+  void* pp = nullptr;         // n vg_point_match records
+  size_t cap_pts = 0, cap_poses = 0, cap_part = 0, cap_out = 0, cap_pp = 0;
+  int n = 0;                  // points of the cloud in xyz
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last vg_score_poses call's kernels (vgx_score_ms)
+};
 // window view for the map kernels, built on the device from DState::xs
 struct WinArg {
   int mp[kMaxWin];      // mp[] ring (octree.cpp:75)
@@ -502,6 +514,8 @@ struct vg_ctx {
   int in_next = 0;
   hipEvent_t in_ev = nullptr;  // the current scan's unpack (the split IEKF stream waits for it)
 
+  bool mapping = true;       // vg_set_mapping: false = the map is read-only (pipeline.cpp frozen_step)
+  vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
   vg_stats stats;
   void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
   // stage timing with HIP events on the context stream (vg_profile)
@@ -867,6 +881,20 @@ int markers_collect(vg_ctx* ctx);          // one collection over surf_map_slide
 int markers_read(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferred);
 int map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n);
 void markers_free(vg_ctx* ctx);
+// score.hip: OctoTree::match for one cloud under K poses (host arrays in, host
+// records out; synchronous on the context stream, which the caller drained).
+// xyz == nullptr: the cloud the last call uploaded
+int score_poses_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* poses, int K,
+                    const double* pose_var, vg_pose_score* out, void* per_point);
+// the IEKF's 34 sums (HTH, HTz, nnt, matches) of the uploaded cloud at one pose
+int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const double* pose_var, double* out34);
+void score_free(vg_ctx* ctx);
+// localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
+int host_set_mapping(vg_ctx* ctx, int on);
+int host_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, int K, const double* pose_var,
+                     vg_pose_score* out, void* per_point);
+int host_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess, const vg_reloc_params* prm,
+                    int install, double* out_pose, vg_pose_score* out_score, int* ok);
 int host_quiesce(vg_ctx* ctx);  // host_sync between scans; inside an open scan the context stream's drain
 int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters);  // kdlio_host.cpp
 int decode_scan(vg_ctx* ctx, const void* records, int n, const vg_lidar_format* fmt, float* xyz, float* inten,

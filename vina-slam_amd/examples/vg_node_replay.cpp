@@ -14,9 +14,14 @@
 //
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
+//        [--map FILE --localize [--guess "x y z yaw"]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
+// --map FILE --localize: load the map FILE (a checkpoint), relocalise on the first scan around the
+// guess (default: the map's saved pose; --guess: position and yaw about z, the saved roll / pitch kept;
+// window +-2 m / 0.25 m, +-30 deg / 2.5 deg) and run with the map frozen; the TUM output is as always.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,18 +33,22 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
-  std::string ck_out, resume;
+  std::string ck_out, resume, map_file, guess_s;
   int ck_at = -1;
+  bool localize = false;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
     if (i + 1 < argc0 && a == "--checkpoint-out") ck_out = argv0[++i];
     else if (i + 1 < argc0 && a == "--checkpoint-at") ck_at = atoi(argv0[++i]);
     else if (i + 1 < argc0 && a == "--resume") resume = argv0[++i];
+    else if (i + 1 < argc0 && a == "--map") map_file = argv0[++i];
+    else if (i + 1 < argc0 && a == "--guess") guess_s = argv0[++i];
+    else if (a == "--localize") localize = true;
     else pos.push_back(argv0[i]);
   }
   const int argc = (int)pos.size();
   char** argv = pos.data();
-  if (argc < 3 || (ck_out.empty() != (ck_at < 0))) {
+  if (argc < 3 || (ck_out.empty() != (ck_at < 0)) || (localize != !map_file.empty())) {
     fprintf(stderr, "usage: %s events.bin out_tum.txt [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]\n", argv[0]);
     return 2;
   }
@@ -88,9 +97,42 @@ int main(int argc0, char** argv0) {
       node.load_checkpoint(resume);
       node.skip_packages(consumed);
     }
+    if (localize) {
+      vina_gpu::NodeParams np;
+      np.localization_mode = 1;
+      np.map_path = map_file;
+      node.apply(np);
+      double st[VG_STATE_LEN], g[12];
+      if (vg_get_state(node.lio().raw(), st) != VG_OK) return 1;
+      memcpy(g, st + 1, sizeof(g));
+      double x, y, z, yaw;
+      if (!guess_s.empty()) {
+        if (sscanf(guess_s.c_str(), "%lf %lf %lf %lf", &x, &y, &z, &yaw) != 4) {
+          fprintf(stderr, "vg_node_replay: --guess wants \"x y z yaw\"\n");
+          return 2;
+        }
+        const double c = cos(yaw), s = sin(yaw), y0 = atan2(g[3], g[0]);
+        const double c0 = cos(-y0), s0 = sin(-y0);  // Rz(yaw) Rz(-yaw0) R: the saved roll / pitch under the new yaw
+        double R1[9], R2[9];
+        for (int k = 0; k < 3; k++) {
+          R1[k] = c0 * g[k] - s0 * g[3 + k], R1[3 + k] = s0 * g[k] + c0 * g[3 + k], R1[6 + k] = g[6 + k];
+        }
+        for (int k = 0; k < 3; k++) {
+          R2[k] = c * R1[k] - s * R1[3 + k], R2[3 + k] = s * R1[k] + c * R1[3 + k], R2[6 + k] = R1[6 + k];
+        }
+        memcpy(g, R2, sizeof(R2));
+        g[9] = x, g[10] = y, g[11] = z;
+      }
+      vg_reloc_params prm;
+      memset(&prm, 0, sizeof(prm));
+      prm.half_xy = 2.0, prm.step_xy = 0.25;
+      prm.half_yaw = 30 * M_PI / 180, prm.step_yaw = 2.5 * M_PI / 180;
+      node.relocalize(g, prm);
+    }
     if (ck_at >= 0) node.set_package_limit(ck_at);
     std::vector<unsigned char> rec;
     int n_imu = 0, n_msg = 0, n_step = 0;
+    bool reloc_said = false;
     for (;;) {
       int type = -1;
       if (!rd(f, &type, 4) || type < 0) break;
@@ -109,6 +151,10 @@ int main(int argc0, char** argv0) {
         n_msg++;
       }
       n_step += node.spin();
+      if (localize && node.relocalized() && !reloc_said) {
+        fprintf(stderr, "relocalise: %s\n", node.relocalize_ok() ? "ok" : "failed (the guess's pose stays)");
+        reloc_said = true;
+      }
       if (ck_at >= 0 && node.packages() >= ck_at) {
         const long long bytes = node.save_checkpoint(ck_out);
         FILE* fmeta = fopen((ck_out + ".meta").c_str(), "w");

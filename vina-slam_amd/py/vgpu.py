@@ -61,6 +61,55 @@ class VgPlaneMarker(ctypes.Structure):
                 ("layer", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class PoseScore(ctypes.Structure):
+    """vg_pose_score (include/vina_gpu.h): one hypothesis' record, 80 bytes."""
+    _fields_ = [("matches", ctypes.c_int32), ("in_map", ctypes.c_int32), ("cost", ctypes.c_double),
+                ("sum_abs", ctypes.c_double), ("nn", ctypes.c_double * 6), ("reserved", ctypes.c_double)]
+
+
+class PointMatch(ctypes.Structure):
+    """vg_point_match: vg_score_poses' per-point record, 24 bytes."""
+    _fields_ = [("leaf", ctypes.c_int32), ("flag", ctypes.c_int32), ("r", ctypes.c_double),
+                ("sigma_d", ctypes.c_double)]
+
+
+class RelocParams(ctypes.Structure):
+    """vg_reloc_params."""
+    _fields_ = [("half_xy", ctypes.c_double), ("step_xy", ctypes.c_double), ("half_z", ctypes.c_double),
+                ("step_z", ctypes.c_double), ("half_yaw", ctypes.c_double), ("step_yaw", ctypes.c_double),
+                ("refine_top", ctypes.c_int), ("refine_iters", ctypes.c_int), ("min_match_ratio", ctypes.c_double),
+                ("reserved", ctypes.c_double * 4)]
+
+
+POSE_SCORE_DTYPE = np.dtype([("matches", "<i4"), ("in_map", "<i4"), ("cost", "<f8"), ("sum_abs", "<f8"),
+                             ("nn", "<f8", 6), ("reserved", "<f8")])
+POINT_MATCH_DTYPE = np.dtype([("leaf", "<i4"), ("flag", "<i4"), ("r", "<f8"), ("sigma_d", "<f8")])
+SCORE_MAX_POSES = 65536
+
+
+def reloc_params(half_xy=0.0, step_xy=0.0, half_z=0.0, step_z=0.0, half_yaw=0.0, step_yaw=0.0, refine_top=8,
+                 refine_iters=8, min_match_ratio=0.5):
+    p = RelocParams()
+    p.half_xy, p.step_xy, p.half_z, p.step_z, p.half_yaw, p.step_yaw = half_xy, step_xy, half_z, step_z, half_yaw, step_yaw
+    p.refine_top, p.refine_iters, p.min_match_ratio = refine_top, refine_iters, min_match_ratio
+    return p
+
+
+def reloc_grid(**params):
+    """vg_reloc_grid: the hypothesis offsets (K, 4) [dx, dy, dz, dyaw] of vg_relocalize, in dispatch order
+    (no device). Raises VgError (-1) for a bad window or more than 65,536 hypotheses."""
+    p = reloc_params(**params)
+    n = ctypes.c_int(0)
+    r = lib().vg_reloc_grid(ctypes.byref(p), None, 0, ctypes.byref(n))
+    if r != 0:
+        raise VgError("vg_reloc_grid failed (%d)" % r)
+    out = np.zeros((n.value, 4))
+    r = lib().vg_reloc_grid(ctypes.byref(p), _d(out), n.value, ctypes.byref(n))
+    if r != 0:
+        raise VgError("vg_reloc_grid failed (%d)" % r)
+    return out
+
+
 # the same layout as a numpy record type (what the marker calls return)
 MARKER_DTYPE = np.dtype([("voxel_center", "<f8", 3), ("quater_length", "<f8"), ("center", "<f8", 3),
                          ("normal", "<f8", 3), ("quat", "<f8", 4), ("plane_scale", "<f8", 3), ("tip", "<f8", 3),
@@ -156,6 +205,14 @@ def lib():
             L.vg_checkpoint_save.argtypes = [P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
             L.vg_checkpoint_load.argtypes = [P, ctypes.c_char_p]
             L.vgx_checkpoint_timed.argtypes = [P, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), dp]
+        L.has_localize = hasattr(L, "vg_score_poses")  # a build older than the localisation calls (A/B runs)
+        if L.has_localize:
+            L.vg_set_mapping.argtypes = [P, ctypes.c_int]
+            L.vg_score_poses.argtypes = [P, fp, ctypes.c_int, dp, ctypes.c_int, dp, P, P]
+            L.vg_reloc_grid.argtypes = [ctypes.POINTER(RelocParams), dp, ctypes.c_int, ip]
+            L.vg_relocalize.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(RelocParams), ctypes.c_int, dp,
+                                        ctypes.POINTER(PoseScore), ip]
+            L.vgx_score_ms.argtypes = [P, dp]
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -388,6 +445,44 @@ class Context:
         out = (ctypes.c_longlong * 6)()
         self._chk(lib().vg_release_far(self.h, (1 if compact else 0) | (2 if census else 0), out), "vg_release_far")
         return list(out)
+
+    def set_mapping(self, on):
+        """vg_set_mapping: False freezes the map (localisation only), True maps again. Between scans."""
+        self._chk(lib().vg_set_mapping(self.h, 1 if on else 0), "vg_set_mapping")
+
+    def score_poses(self, xyz, poses, pose_var=None, per_point=False):
+        """vg_score_poses: the scan xyz (n, 3; LiDAR frame) under the K poses (K, 12) [R row-major, p].
+        Returns the K records (POSE_SCORE_DTYPE); with per_point (K = 1) also the n POINT_MATCH_DTYPE records."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        pv = None if pose_var is None else np.ascontiguousarray(pose_var, dtype=np.float64).reshape(18)
+        out = np.zeros(max(poses.shape[0], 1), dtype=POSE_SCORE_DTYPE)
+        pp = np.zeros(max(xyz.shape[0], 1), dtype=POINT_MATCH_DTYPE) if per_point else None
+        self._chk(lib().vg_score_poses(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0], _d(poses),
+                                       poses.shape[0], None if pv is None else _d(pv), out.ctypes.data,
+                                       None if pp is None else pp.ctypes.data), "vg_score_poses")
+        out = out[: poses.shape[0]]
+        return (out, pp[: xyz.shape[0]]) if per_point else out
+
+    def score_ms(self):
+        """Device time of the last score_poses call's kernels (HIP events on the context stream), ms."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_score_ms(self.h, ctypes.byref(ms)), "vgx_score_ms")
+        return ms.value
+
+    def relocalize(self, xyz, guess, install=False, **params):
+        """vg_relocalize: (pose (12,), the refined winner's record, ok). guess: (12,) [R, p]; params: reloc_params."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        g = np.ascontiguousarray(guess, dtype=np.float64).reshape(12)
+        p = reloc_params(**params)
+        pose = np.zeros(12)
+        sc = PoseScore()
+        ok = ctypes.c_int(0)
+        self._chk(lib().vg_relocalize(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0], _d(g), ctypes.byref(p),
+                                      1 if install else 0, _d(pose), ctypes.byref(sc), ctypes.byref(ok)),
+                  "vg_relocalize")
+        rec = {"matches": sc.matches, "in_map": sc.in_map, "cost": sc.cost, "sum_abs": sc.sum_abs, "nn": list(sc.nn)}
+        return pose, rec, bool(ok.value)
 
     def _need_checkpoint(self):
         if not lib().has_checkpoint:

@@ -65,6 +65,10 @@ class VinaNode : public rclcpp::Node {
     // checkpoint and resume (vg_checkpoint_save / vg_checkpoint_load): written at shutdown / loaded at start-up
     checkpoint_path_ = declare_parameter("General.checkpoint_path", std::string(""));
     const std::string resume_from = declare_parameter("General.resume_from", std::string(""));
+    // localisation in a saved map (NodeCore::apply): 1 = load General.map_path and run with the map frozen
+    vina_gpu::NodeParams loc;
+    loc.localization_mode = (int)declare_parameter("General.localization_mode", 0);
+    loc.map_path = declare_parameter("General.map_path", std::string(""));
     c.odo_cov_gyr = declare_parameter("Odometry.cov_gyr", 0.1);
     c.odo_cov_acc = declare_parameter("Odometry.cov_acc", 0.1);
     c.odo_rdw_gyr = declare_parameter("Odometry.rdw_gyr", 1e-4);
@@ -103,6 +107,7 @@ class VinaNode : public rclcpp::Node {
     vg_capacity cap = {0, 0, 0, 0};
     core_ = std::make_unique<vina_gpu::NodeCore>(c, &cap, fmt_, point_notime);
     if (!resume_from.empty()) core_->load_checkpoint(resume_from);  // (a live node: no package to skip)
+    core_->apply(loc);
     if (enable_visualization) core_->enable_visualization(true);  // before the first scan
 
     rclcpp::QoS imu_qos(8000);
