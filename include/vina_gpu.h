@@ -391,6 +391,47 @@ int vg_reloc_grid(const vg_reloc_params* prm, double* out, int cap, int* count);
 int vg_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess_pose,
                   const vg_reloc_params* prm, int install, double* out_pose, vg_pose_score* out_score, int* ok);
 
+/* ---- Map views: many sensors in one frozen map ------------------------------
+ * vg_map_attach makes `tracker` a read-only view of `owner`'s map: every kernel
+ * of the tracker that reads the map (the IEKF, vg_score_poses, vg_relocalize,
+ * vg_map_planes) takes the owner's pointers, so B sensors localising in one
+ * map hold it once. A tracker is an ordinary context and may be created with
+ * tiny map capacities (e.g. max_nodes 1024, max_fix_points 1024, hash_log2
+ * 10): it then costs its scan staging, IEKF work buffers and state, not a map.
+ * Its own map stays allocated and comes back on the detach. A context that has
+ * stepped scans before may attach: whatever it captured for its own map is
+ * dropped on attach and on detach.
+ * Attach requires (else VG_E_STATE, or VG_E_ARG where noted; vg_last_error of
+ * either context names the failed check): the owner has mapping off; both
+ * contexts on the same device (VG_E_ARG); both unsharded; neither inside a
+ * scan; their vg_config equal byte for byte (VG_E_ARG); the tracker neither
+ * attached already nor itself an owner; the owner not itself attached; the
+ * owner's window fits the tracker's max_points_per_scan (VG_E_ARG).
+ * Attach completes both contexts' outstanding work and installs the owner's
+ * between-scans estimator into the tracker, through memory: afterwards the
+ * tracker is what a context that loaded the owner's checkpoint and froze it
+ * would be (state, window, last_pcl_end_time, trajectory and path rows,
+ * vg_stats' nodes_used and fix_used; stats_log restarts), with mapping off.
+ * vg_seed or vg_relocalize(install) then moves it to where its sensor is.
+ * While attached, on the tracker: vg_step*, vg_seed, vg_score_poses,
+ * vg_relocalize, vg_map_planes, the state / stats / trajectory / path / poll
+ * accessors work as on a frozen context, and vg_release_far reports the census
+ * only. VG_E_STATE: vg_set_mapping(tracker, 1), vg_checkpoint_save,
+ * vg_checkpoint_load, vg_reset, vg_set_publish with either bit, vg_shard_*,
+ * vg_profile with the per-stage bit (its P_k pass writes the map's stamps).
+ * vg_destroy(tracker) detaches first.
+ * While an owner has views these return VG_E_STATE and change nothing:
+ * vg_set_mapping(owner, 1), vg_reset, vg_checkpoint_load, vg_checkpoint_save
+ * (it compacts, so node ids move), vg_release_far with the compaction flag
+ * (without it: the census only), vg_shard_*, vg_destroy. The owner may still
+ * step frozen scans itself.
+ * vg_map_detach (VG_E_STATE when not attached, inside a scan, or in a fleet)
+ * completes the tracker's work and hands its own map back, empty, with the
+ * context as after vg_reset and mapping still off: the window it followed
+ * belongs to the owner's map. Read its trajectory before detaching. */
+int vg_map_attach(vg_ctx* tracker, vg_ctx* owner);
+int vg_map_detach(vg_ctx* tracker);
+
 /* Window states x_buf (win_count x 250 doubles); returns win_count via *n. */
 int vg_window_states(vg_ctx* ctx, double* out, int* n);
 
@@ -618,6 +659,42 @@ int vg_multi_step_dev(vg_multi* mv, const vg_scan_dev* scans);
 int vg_multi_set_active(vg_multi* mv, int cap);
 int vg_multi_sync(vg_multi* mv);
 void vg_multi_destroy(vg_multi* mv);
+
+/* The fleet: B trackers attached to one owner's map (vg_map_attach) stepped
+ * together, one frozen scan each per step, in ten kernel launches on one
+ * stream for any B (the opening, four IEKF point loops over a (blocks, B)
+ * grid, four updates, the publication). Each tracker's results are a lone
+ * frozen context's, bit for bit, whatever the batch.
+ * vg_fleet_create: B >= 1; every tracker attached to `owner`, none inside a
+ * scan or in another fleet, all with the same max_points_per_scan (one IEKF
+ * grid, and with it one reduction tree, serves all); else VG_E_STATE / VG_E_ARG.
+ * Completes the trackers' outstanding work. While the fleet exists its
+ * trackers are stepped only through it: vg_step*, vg_propagate, vg_map_detach
+ * and vg_destroy on them return VG_E_STATE; their accessors work as usual.
+ * vg_fleet_step_dev: B records; n < 0: tracker b sits this step out (nothing of
+ * it moves). d_time != NULL: the scan is deskewed first. Returns once the work
+ * is enqueued; the scans' arrays must stay valid until the step's results are
+ * read. n == 0 is an empty scan (its planes may be NULL): the tracker
+ * propagates and its IEKF runs on no points. Queues every participating scan
+ * or none: a bad record (VG_E_ARG, VG_E_CAPACITY) or a tracker's deferred error
+ * is returned before anything is propagated or enqueued, and the fleet stays
+ * usable. A failure past those checks (a HIP error, or a tracker's propagation
+ * or deskew failing, e.g. more IMU segments than the deskew holds) cannot be
+ * undone: nothing of the step is launched, but the trackers ahead of the
+ * failing one have propagated (their opened scans are abandoned), so the fleet
+ * is out of step; every later vg_fleet_step_dev and vg_fleet_sync returns that error,
+ * and the way on is vg_fleet_destroy, then vg_map_detach + vg_map_attach of
+ * each tracker (the detach resets it). A fleet step runs no downsample, nothing downstream of it existing
+ * in a frozen map: for fleet-stepped scans vg_stats::n_ds is 0 and
+ * vg_scan_points returns 0 points (vg_downsample gives the cloud). vg_profile's
+ * in-kernel clocks and launch events do not cover fleet steps.
+ * vg_fleet_sync completes every tracker's enqueued scans and returns the first
+ * error. vg_fleet_destroy hands the trackers back, still attached. */
+typedef struct vg_fleet vg_fleet;
+int vg_fleet_create(vg_ctx* owner, vg_ctx** trackers, int B, vg_fleet** out);
+int vg_fleet_step_dev(vg_fleet* f, const vg_scan_dev* scans);
+int vg_fleet_sync(vg_fleet* f);
+void vg_fleet_destroy(vg_fleet* f);
 
 #ifdef __cplusplus
 }

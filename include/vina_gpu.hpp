@@ -126,6 +126,10 @@ class LioCore {
     check(vg_relocalize(ctx_, xyz, n, guess_pose, &prm, install ? 1 : 0, out_pose, score, &ok), "vg_relocalize");
     return ok != 0;
   }
+  // map views (vina_gpu.h "Map views"): this context reads owner's frozen map. The owner
+  // must outlive its views: destroy (or detach) the trackers first
+  void attach(LioCore& owner) { check(vg_map_attach(ctx_, owner.ctx_), "vg_map_attach"); }
+  void detach() { check(vg_map_detach(ctx_), "vg_map_detach"); }
   void marker_capacity(int max_records) { check(vg_marker_capacity(ctx_, max_records), "vg_marker_capacity"); }
   std::vector<vg_plane_marker> markers(int* deferred = nullptr) {
     int n = 0, d = 0;
@@ -151,6 +155,33 @@ class LioCore {
     if (r != VG_OK) throw Error(r, std::string(what) + ": " + vg_last_error(ctx_));
   }
   vg_ctx* ctx_ = nullptr;
+};
+
+// The fleet (vg_fleet_*): trackers attached to one owner's map, one frozen scan
+// each per step in ten launches for any number of trackers. Destroy the fleet
+// before its trackers.
+class Fleet {
+ public:
+  Fleet(LioCore& owner, const std::vector<LioCore*>& trackers) {
+    std::vector<vg_ctx*> c;
+    for (LioCore* t : trackers) c.push_back(t->raw());
+    const int r = vg_fleet_create(owner.raw(), c.data(), (int)c.size(), &f_);
+    if (r != VG_OK) throw Error(r, std::string("vg_fleet_create: ") + vg_last_error(owner.raw()));
+    first_ = c.empty() ? nullptr : c[0];
+  }
+  ~Fleet() { vg_fleet_destroy(f_); }
+  Fleet(const Fleet&) = delete;
+  Fleet& operator=(const Fleet&) = delete;
+  // one record per tracker; n < 0: the tracker sits the step out
+  void step(const std::vector<vg_scan_dev>& scans) { check(vg_fleet_step_dev(f_, scans.data()), "vg_fleet_step_dev"); }
+  void sync() { check(vg_fleet_sync(f_), "vg_fleet_sync"); }
+
+ private:
+  void check(int r, const char* what) {
+    if (r != VG_OK) throw Error(r, std::string(what) + ": " + vg_last_error(first_));
+  }
+  vg_fleet* f_ = nullptr;
+  vg_ctx* first_ = nullptr;
 };
 
 }  // namespace vina_gpu

@@ -17,104 +17,8 @@ namespace vg {
 // (descend, match_leaf, inside, the matched point's sums and the halving wave
 // sums: vg_match.h, shared with score.hip)
 
-// The pose (x_curr R, p and the rotation / translation covariance blocks) is
-// read from the device state the previous k_iekf_update wrote; the kernel is a
-// no-op once the IEKF has finished (st->done). Iteration 0 ignores the leaf
-// cache (no association yet, odometry.cpp:111-132).
-// one IEKF iteration's point loop over the workgroup's chunk vb (k_iekf): the
-// 34 sums of this lane's points
-// kPf: a point whose cached leaf matched last iteration (octos[i]) touches its
-// plane record's 128 B lines right away, beside the header load, so the
-// gate's record reads hit in cache instead of a second dependent miss
-template <bool kPf = false>
-__device__ __forceinline__ void iekf_points(const MP& mp, const DState* __restrict__ st, const DevMap& m,
-                                            int* __restrict__ cache, int* __restrict__ pk, int it, int nb, int vb,
-                                            const M3& R, const V3& p, const M3& rot_var, const M3& tsl_var,
-                                            double (&acc)[kIekfVals]) {
-  const int* __restrict__ keep = iekf_keep(st);
-  const int n = keep ? st->snk : st->sn;
-  const float* __restrict__ x = st->sx;
-  const float* __restrict__ y = st->sy;
-  const float* __restrict__ z = st->sz;
-  const M3 Rt = tr(R);
-  for (int j = 0; j < kIekfVals; j++) acc[j] = 0.0;
-  for (int q = vb * blockDim.x + threadIdx.x; q < n; q += nb * blockDim.x) {
-    const int i = keep ? keep[q] : q;  // the raw index (the memo and the profiling pass are per raw point)
-    V3 pnt;
-    M3 var;
-    var_init_pt(mp, x[i], y[i], z[i], pnt, var);
-    M3 var_world = world_var(R, var, pnt, rot_var, tsl_var);
-    V3 wld = rigid(R, pnt, p);
-    // cache[i]: the leaf of the point's last match (the reference's octos[i],
-    // odometry.cpp:124-131, reset per scan) or, after a failed match, the
-    // leaf the descent reached — a memo only (bit 30 tags it): while the
-    // point stays inside that leaf's box and its float voxel key still names
-    // the leaf's root (the lookup rounds in float, voxel_map.cpp:246-253), the
-    // lookup would reach the same leaf, so unmatched points skip the hash +
-    // descent too
-    const int cv = it > 0 ? cache[i] : -1;
-    int leaf = cv >= 0 ? (cv & 0x3fffffff) : -1;
-    int flag = 0;
-    double sigma = 0;
-    double pf0 = 0.0, pf1 = 0.0, pf2 = 0.0;
-    if (kPf && cv >= 0 && !(cv & 0x40000000)) {  // bytes 0, 112, 216: every 128 B line the 224 B record spans
-      const double* rec = reinterpret_cast<const double*>(&m.pl[leaf]);
-      pf0 = rec[0];
-      pf1 = rec[14];
-      pf2 = rec[27];
-    }
-    // a matched leaf (octos[i]): OctoTree::inside's inclusive box; a memo: the
-    // descent's own region (dbox: strict where the descent is strict), so a
-    // point on a centre plane is never kept in the wrong sibling
-    bool hit = leaf >= 0 && ((cv & 0x40000000) ? in_dbox(m.dbox + (size_t)leaf * 6, wld) : inside(m.hdr[leaf], wld));
-    if (hit && (cv & 0x40000000)) {
-      uint64_t kw, kl;
-      const NodeHdr& hl = m.hdr[leaf];
-      hit = pack_key(wld, mp.vs, kw) && pack_key(v3(hl.center[0], hl.center[1], hl.center[2]), mp.vs, kl) && kw == kl;
-    }
-    if (hit) {
-      if (kPf) asm volatile("" ::"v"(pf0), "v"(pf1), "v"(pf2));  // the touches complete here, not before
-      flag = match_leaf(m.hdr[leaf], m.pl[leaf], wld, var_world, sigma);
-      if (!flag && !(cv & 0x40000000)) leaf = -2;  // the reference's octos[i] stays: keep the cache
-    } else {
-      leaf = -1;
-      uint64_t key;
-      if (pack_key(wld, mp.vs, key) && owns(m, key)) {  // another shard's tile: not matched here
-        int root = hash_find(m.hkey, m.hval, m.hash_mask, key);
-        int lf = root >= 0 ? descend(m.hdr, root, wld) : -1;
-        if (lf >= 0) {
-          flag = match_leaf(m.hdr[lf], m.pl[lf], wld, var_world, sigma);
-          leaf = lf;
-        }
-      }
-    }
-    if (pk) pk[i] = flag ? leaf : -1;  // the leaf whose plane this iteration read (profiling pass)
-    if (flag) {
-      cache[i] = leaf;
-    } else if (leaf >= 0) {
-      if (it == 0 || cv < 0 || (cv & 0x40000000)) cache[i] = leaf | 0x40000000;  // no octos[i] to keep
-    } else if (leaf == -1 && (it == 0 || cv < 0 || (cv & 0x40000000))) {
-      cache[i] = -1;
-    }
-    if (flag) iekf_accum(acc, m.pl[leaf], pnt, Rt, wld, sigma);
-  }
-}
-// (iekf_wg_sum, the workgroup's 34 sums: vg_match.h)
-// the pose words an iteration's point loop reads from x_curr: R 9, p 3, the
-// rotation and translation covariance blocks 9 + 9
-__device__ __forceinline__ double pose_word(const double* xc, int t) {
-  if (t < 12) return xc[t];
-  if (t < 21) return xc[kXS + ((t - 12) / 3) * 15 + (t - 12) % 3];
-  return xc[kXS + (3 + (t - 21) / 3) * 15 + 3 + (t - 21) % 3];
-}
-__device__ __forceinline__ void pose_of(const double* w, M3& R, V3& p, M3& rot_var, M3& tsl_var) {
-  for (int q = 0; q < 9; q++) {
-    R[q] = w[q];
-    rot_var[q] = w[12 + q];
-    tsl_var[q] = w[21 + q];
-  }
-  p = v3(w[9], w[10], w[11]);
-}
+// (iekf_points, the point loop of one workgroup, and pose_word / pose_of: vg_match.h,
+// shared with the fleet's batched launches, fleet.hip)
 
 template <bool kPf>
 __global__ void __launch_bounds__(256) k_iekf(MP mp, DState* __restrict__ st, int it, DevMap m,

@@ -320,8 +320,10 @@ int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, lo
     fix_new = tail[2] + tail[3];
     // compact when the release erased something, when asked, or when over half
     // of the point_fix arena is abandoned blocks
-    const bool go = n > 0 && (hcnt[kRelDead] > 0 || hcnt[kRelGarbage] > 0 || compact ||
-                              (long)nfix_used > 2l * (long)fix_new);
+    // (a map view, vg_map_attach: the census only on either side, node ids must not move)
+    const bool shared = ctx->view_of != nullptr || ctx->views > 0;
+    const bool go = !shared && n > 0 && (hcnt[kRelDead] > 0 || hcnt[kRelGarbage] > 0 || compact ||
+                                         (long)nfix_used > 2l * (long)fix_new);
     if (!go) return VG_OK;
     did = true;
     // the gather buffer: the largest per-node array of the kept nodes, the kept point_fix blocks, the hash pairs

@@ -16,6 +16,10 @@ namespace vg {
 // scan's margi tail (and whatever device flag it publishes) is done before the
 // first frozen scan is enqueued, and no hand-off of the split IEKF is left armed
 int host_set_mapping(vg_ctx* ctx, int on) {
+  if (on) {  // a map other contexts read, or another context's map, stays read-only
+    VG_TRY(refuse_attached(ctx, "vg_set_mapping"));
+    VG_TRY(refuse_owner(ctx, "vg_set_mapping"));
+  }
   VG_TRY(host_ckpt_allowed(ctx, "vg_set_mapping", true));  // open scan, cold start initialising, sharded world > 1
   VG_TRY(host_sync(ctx));
   if (ctx->stream_ds && ctx->stream_ds != ctx->stream) VG_HIP(hipStreamSynchronize(ctx->stream_ds));
@@ -24,6 +28,116 @@ int host_set_mapping(vg_ctx* ctx, int on) {
   ctx->sync_tail_armed = false;
   ctx->mapping = on != 0;
   return VG_OK;
+}
+
+// ---- map views (vina_gpu.h "Map views"): a tracker reads the owner's frozen map
+static int drain_all(vg_ctx* ctx) {
+  VG_TRY(host_sync(ctx));
+  if (ctx->stream_ds && ctx->stream_ds != ctx->stream) VG_HIP(hipStreamSynchronize(ctx->stream_ds));
+  if (ctx->stream_iekf) VG_HIP(hipStreamSynchronize(ctx->stream_iekf));
+  return VG_OK;
+}
+
+// After the attach the tracker is what a context that loaded the owner's
+// checkpoint and froze it would be, without the file and without the map's
+// copy: the load's own steps (checkpoint.hip checkpoint_load) on the owner's
+// memory — vg_reset, DState's semantic fields (the checkpoint's list), the host
+// mirror through its blob (ckpt_host.cpp) — and then the owner's DevMap in
+// place of the tracker's own, which waits in own_map
+int host_map_attach(vg_ctx* ctx, vg_ctx* owner) {
+  const char* who = "vg_map_attach";
+  auto refuse = [&](const char* why, int code) {
+    ctx->err = std::string(who) + ": " + why;
+    owner->err = ctx->err;
+    return code;
+  };
+  if (ctx == owner) return refuse("a context cannot attach to itself", VG_E_ARG);
+  if (ctx->device != owner->device) return refuse("the contexts are on different devices", VG_E_ARG);
+  if (memcmp(&ctx->cfg, &owner->cfg, sizeof(vg_config)) != 0)
+    return refuse("the contexts' vg_config differ (they must be equal byte for byte)", VG_E_ARG);
+  if (ctx->view_of) return refuse("the tracker is already attached (vg_map_detach first)", VG_E_STATE);
+  if (ctx->views > 0) return refuse("the tracker is itself an owner (contexts are attached to it)", VG_E_STATE);
+  if (owner->view_of) return refuse("the owner is itself attached to another context's map", VG_E_STATE);
+  if (ctx->fleet || owner->fleet) return refuse("a fleet's tracker cannot attach or be attached to", VG_E_STATE);
+  if (owner->mapping) return refuse("the owner is mapping (vg_set_mapping(owner, 0) first)", VG_E_STATE);
+  if (sharded(ctx) || sharded(owner)) return refuse("a context is sharded", VG_E_STATE);
+  if (hp(ctx)->in_scan || hp(owner)->in_scan) return refuse("a context is inside a scan (vg_step_end first)", VG_E_STATE);
+  if (init_active(hp(owner))) return refuse("the owner's cold-start initialisation is still running", VG_E_STATE);
+  VG_TRY(drain_all(owner));
+  VG_TRY(drain_all(ctx));
+  std::vector<unsigned char> blob;
+  host_ckpt_blob(owner, blob);
+  void* snap = nullptr;
+  // the one thing the blob's parser checks against the receiving context's capacity, named here
+  for (int i = 0; i < 32; i++)
+    if (hp(owner)->wp_n[i] > ctx->cap.max_points_per_scan)
+      return refuse("a scan of the owner's window is larger than the tracker's max_points_per_scan", VG_E_ARG);
+  if (host_ckpt_parse(ctx, blob.data(), blob.size(), &snap) != VG_OK)
+    return refuse("the owner's host state did not parse (host_ckpt_parse refused the blob host_ckpt_blob wrote)",
+                  VG_E_STATE);
+  // ---- every check passed: from here the tracker is rewritten
+  int r = vg_reset(ctx);
+  if (r != VG_OK) {
+    host_ckpt_drop(snap);
+    return r;
+  }
+  {
+    DState* d = ctx->st;
+    const DState* s = owner->st;
+    hipError_t e = hipSuccess;
+    auto field = [&](void* dst, const void* src, size_t bytes) {
+      if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice);
+    };
+    field(d->xc, s->xc, sizeof(d->xc));
+    field(d->xp, s->xp, sizeof(d->xp));
+    field(d->G6, s->G6, sizeof(d->G6));
+    field(d->nnt, s->nnt, sizeof(d->nnt));
+    field(d->traj, s->traj, sizeof(d->traj));
+    field(d->xs, s->xs, sizeof(d->xs));
+    field(d->bias, s->bias, sizeof(d->bias));
+    field(&d->jour, &s->jour, sizeof(double));
+    field(d->last_pos, s->last_pos, sizeof(d->last_pos));
+    field(d->imurec, s->imurec, sizeof(d->imurec));
+    field(&d->imu_head, &s->imu_head, sizeof(int));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      host_ckpt_drop(snap);
+      ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+      return VG_E_HIP;
+    }
+  }
+  host_ckpt_install(ctx, snap);
+  ctx->tail_a_valid = false;
+  ctx->sync_tail_armed = false;
+  ctx->mapping = false;
+  graphs_drop(ctx);  // a graph captured on the tracker's own map (it stepped before) must not be replayed on the view
+  ctx->own_map = ctx->map;
+  ctx->map = owner->map;
+  ctx->view_of = owner;
+  owner->views++;
+  return VG_OK;
+}
+
+// The tracker's own map comes back, empty as the attach's reset left it, and
+// with it a fresh context (vg_reset): the window the tracker followed belongs
+// to the owner's map and means nothing in an empty one. Mapping stays off.
+int host_map_detach(vg_ctx* ctx) {
+  if (!ctx->view_of) {
+    ctx->err = "vg_map_detach: the context is not attached";
+    return VG_E_STATE;
+  }
+  VG_TRY(refuse_fleet(ctx, "vg_map_detach"));
+  if (hp(ctx)->in_scan) {
+    ctx->err = "vg_map_detach inside a scan (vg_step_end first)";
+    return VG_E_STATE;
+  }
+  (void)drain_all(ctx);  // (a deferred error goes with the state the reset drops)
+  (void)hipStreamSynchronize(ctx->stream);  // nothing of the tracker's reads the owner's map past this point
+  graphs_drop(ctx);  // the IEKF graph captured while attached holds the owner's pointers
+  ctx->map = ctx->own_map;
+  ctx->view_of->views--;
+  ctx->view_of = nullptr;
+  return vg_reset(ctx);
 }
 
 int host_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, int K, const double* pose_var,
@@ -212,6 +326,14 @@ extern "C" {
 int vg_set_mapping(vg_ctx* ctx, int on) {
   if (!ctx) return VG_E_ARG;
   return vg::host_set_mapping(ctx, on);
+}
+int vg_map_attach(vg_ctx* tracker, vg_ctx* owner) {
+  if (!tracker || !owner) return VG_E_ARG;
+  return vg::host_map_attach(tracker, owner);
+}
+int vg_map_detach(vg_ctx* tracker) {
+  if (!tracker) return VG_E_ARG;
+  return vg::host_map_detach(tracker);
 }
 int vg_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, int K, const double* pose_var,
                    vg_pose_score* out, void* per_point) {

@@ -182,6 +182,8 @@ static int shard_common(vg_ctx* ctx, int rank, int world) {
     ctx->err = "vg_shard: rank/world out of range";
     return VG_E_ARG;
   }
+  VG_TRY(refuse_attached(ctx, "vg_shard"));  // a map view (vg_map_attach) is unsharded on both sides
+  VG_TRY(refuse_owner(ctx, "vg_shard"));
   if (host_win_count(ctx) != 0 || ctx->shard.mode != 0) {
     ctx->err = "vg_shard: call once, before the first scan";
     return VG_E_STATE;

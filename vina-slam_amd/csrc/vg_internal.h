@@ -515,6 +515,12 @@ struct vg_ctx {
   hipEvent_t in_ev = nullptr;  // the current scan's unpack (the split IEKF stream waits for it)
 
   bool mapping = true;       // vg_set_mapping: false = the map is read-only (pipeline.cpp frozen_step)
+  // map views (vg_map_attach, localize.cpp): a tracker's `map` holds the owner's
+  // pointers, read-only; its own records wait in own_map until the detach
+  vg_ctx* view_of = nullptr;  // attached: the owner
+  int views = 0;              // an owner: the trackers attached to its map
+  vg::DevMap own_map;         // an attached tracker's own map
+  void* fleet = nullptr;      // a fleet's tracker (vg_fleet_create): stepped only through the fleet
   vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
   vg_stats stats;
   void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
@@ -857,6 +863,7 @@ int dev_ctx_count(int device);
 // contexts (one-time work per context): the multi-sequence mode's worker
 // threads otherwise capture concurrently (B = 16: sixteen threads at once).
 std::recursive_mutex& capture_mutex();
+void graphs_drop(vg_ctx* ctx);  // destroy every captured graph (vina_gpu.cpp): ctx->map is about to name other memory
 int host_release_far(vg_ctx* ctx, int flags, long long* out);
 bool host_release_pending(vg_ctx* ctx);  // jour advanced in an absorbed scan since the last release
 // lifetime.hip: the journey release + the node pool / point_fix arena compaction
@@ -891,6 +898,41 @@ int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const doub
 void score_free(vg_ctx* ctx);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
+int host_map_attach(vg_ctx* tracker, vg_ctx* owner);
+int host_map_detach(vg_ctx* tracker);
+// what a map view rules out (vina_gpu.h "Map views"): VG_E_STATE with the reason in ctx->err
+inline int refuse_attached(vg_ctx* ctx, const char* who) {
+  if (!ctx->view_of) return VG_OK;
+  ctx->err = std::string(who) + ": the context is attached to another context's map (vg_map_detach first)";
+  return VG_E_STATE;
+}
+inline int refuse_owner(vg_ctx* ctx, const char* who) {
+  if (ctx->views == 0) return VG_OK;
+  ctx->err = std::string(who) + ": " + std::to_string(ctx->views) +
+             " context(s) are attached to this context's map (vg_map_detach them first)";
+  return VG_E_STATE;
+}
+inline int refuse_fleet(vg_ctx* ctx, const char* who) {
+  if (!ctx->fleet) return VG_OK;
+  ctx->err = std::string(who) + ": the context is a fleet's tracker (vg_fleet_step_dev steps it; vg_fleet_destroy first)";
+  return VG_E_STATE;
+}
+// fleet.hip: the batched launches of one fleet step (fleet_host.cpp)
+struct FleetIn {  // one tracker's opening, host-mapped: written by the host before the step's launches
+  double xc[kXC];            // x_curr after the propagation
+  const float *x, *y, *z;    // the scan
+  int n, active;             // active 0: the tracker sits this step out
+  int win_count, seq1, seq2, pad;  // the publication (k_publish_state / k_publish_counters)
+};
+struct FleetTab {  // one tracker's device memory (constant while the fleet lives)
+  DState* st;
+  int* cache;        // Work::iekf_cache
+  double* partials;  // Work::partials
+  Pub* pub;          // the tracker's own publication block (device address)
+  int* act;          // this step's active flag on the device (k_fleet_open)
+};
+int fleet_launch(hipStream_t s, const MP& mp, const DevMap& m, const FleetIn* in, const FleetTab* tab, int B, int nb,
+                 bool prefetch, std::string* err);
 int host_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, int K, const double* pose_var,
                      vg_pose_score* out, void* per_point);
 int host_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess, const vg_reloc_params* prm,

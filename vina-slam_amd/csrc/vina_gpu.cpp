@@ -112,6 +112,25 @@ std::recursive_mutex& capture_mutex() {
   static std::recursive_mutex mu;
   return mu;
 }
+// Every captured graph of the context, destroyed and forgotten (each is
+// captured again on its next use). A graph holds its kernels' arguments as
+// they were at the capture, the DevMap among them, by value: whenever
+// ctx->map comes to name other memory (vg_map_attach / vg_map_detach) the
+// graphs captured before would go on reading the old map. The caller has
+// drained the context's streams.
+void graphs_drop(vg_ctx* ctx) {
+  auto drop = [](hipGraphExec_t& g) {
+    if (g) (void)hipGraphExecDestroy(g);
+    g = nullptr;
+  };
+  for (auto& g : ctx->g_iekf) drop(g);
+  for (auto& g : ctx->g_margi) drop(g);
+  drop(ctx->g_ba);
+  drop(ctx->g_ba2);
+  drop(ctx->g_ds);
+  for (auto& g : ctx->g_mid) drop(g);
+  for (auto& g : ctx->g_scan) drop(g);
+}
 }  // namespace vg
 
 // VG_SEGV_TRACE=1: a fatal signal prints the native stack (the frames of this
@@ -289,6 +308,15 @@ int vg_create(const vg_config* cfg, const vg_capacity* cap, int device, vg_ctx**
 
 int vg_destroy(vg_ctx* ctx) {
   if (!ctx) return VG_OK;
+  // a map other contexts read, or a fleet's tracker, stays; a tracker lets go of the owner's map first
+  VG_TRY(refuse_owner(ctx, "vg_destroy"));
+  VG_TRY(refuse_fleet(ctx, "vg_destroy"));
+  if (ctx->view_of) {
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    ctx->map = ctx->own_map;
+    ctx->view_of->views--;
+    ctx->view_of = nullptr;
+  }
   // a pending LM (vg_step returned before its outcome) needs nothing more:
   // its speculative tail either ran or ran as no-ops, and nothing waits on it
   ctx->ba_loop.active = false;
@@ -315,17 +343,7 @@ int vg_destroy(vg_ctx* ctx) {
   for (int i = 0; i < 10; i++)
     for (int j = 0; j < 2; j++)
       if (ctx->solve_ev[i][j]) (void)hipEventDestroy(ctx->solve_ev[i][j]);
-  for (auto& g : ctx->g_iekf)
-    if (g) (void)hipGraphExecDestroy(g);
-  for (auto& g : ctx->g_margi)
-    if (g) (void)hipGraphExecDestroy(g);
-  if (ctx->g_ba) (void)hipGraphExecDestroy(ctx->g_ba);
-  if (ctx->g_ba2) (void)hipGraphExecDestroy(ctx->g_ba2);
-  if (ctx->g_ds) (void)hipGraphExecDestroy(ctx->g_ds);
-  for (auto& g : ctx->g_mid)
-    if (g) (void)hipGraphExecDestroy(g);
-  for (auto& g : ctx->g_scan)
-    if (g) (void)hipGraphExecDestroy(g);
+  graphs_drop(ctx);
   if (ctx->h_in) (void)hipHostFree(ctx->h_in);
   if (ctx->stream_ds && ctx->stream_ds != ctx->stream) (void)hipStreamSynchronize(ctx->stream_ds);
   delete static_cast<CopyPool*>(ctx->copy_pool);
@@ -357,6 +375,8 @@ void* vg_stream(vg_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 int vg_reset(vg_ctx* ctx) {
   if (!ctx) return VG_E_ARG;
+  VG_TRY(refuse_attached(ctx, "vg_reset"));
+  VG_TRY(refuse_owner(ctx, "vg_reset"));
   VG_HIP(hipStreamSynchronize(ctx->stream_ds));
   VG_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->stream_iekf) VG_HIP(hipStreamSynchronize(ctx->stream_iekf));
@@ -555,6 +575,7 @@ int vg_step(vg_ctx* ctx, const float* xyz, const float* intensity, int n, double
             double pcl_end_time, const double* imu, int m) {
   if (n > 0 && !xyz) return VG_E_ARG;
   VG_TRY(check_scan(ctx, n, m, imu));
+  VG_TRY(refuse_fleet(ctx, "vg_step"));
   if (n == 0) return host_step(ctx, ctx->d_x, ctx->d_y, ctx->d_z, ctx->d_i, n, pcl_beg_time, pcl_end_time, imu, m);
   float* p[5];
   int slot = 0;
@@ -566,6 +587,7 @@ int vg_step_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const float* d_
                 double pcl_beg_time, double pcl_end_time, const double* imu, int m) {
   if (n > 0 && (!d_x || !d_y || !d_z)) return VG_E_ARG;
   VG_TRY(check_scan(ctx, n, m, imu));
+  VG_TRY(refuse_fleet(ctx, "vg_step"));
   return host_step(ctx, d_x, d_y, d_z, d_intensity, n, pcl_beg_time, pcl_end_time, imu, m);
 }
 
@@ -574,6 +596,7 @@ int vg_step_deskew_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const fl
                        int m) {
   if (n > 0 && (!d_x || !d_y || !d_z || !d_time)) return VG_E_ARG;
   VG_TRY(check_scan(ctx, n, m, imu));
+  VG_TRY(refuse_fleet(ctx, "vg_step"));
   return host_step_deskew(ctx, d_x, d_y, d_z, d_intensity, d_time, n, pcl_beg_time, pcl_end_time, imu, m);
 }
 
@@ -581,6 +604,7 @@ int vg_step_deskew(vg_ctx* ctx, const float* xyz, const float* intensity, const 
                    double pcl_beg_time, double pcl_end_time, const double* imu, int m) {
   if (n > 0 && (!xyz || !time)) return VG_E_ARG;
   VG_TRY(check_scan(ctx, n, m, imu));
+  VG_TRY(refuse_fleet(ctx, "vg_step"));
   if (n == 0)
     return host_step_deskew(ctx, ctx->d_x, ctx->d_y, ctx->d_z, ctx->d_i, ctx->d_t, n, pcl_beg_time, pcl_end_time, imu,
                             m);
@@ -624,6 +648,7 @@ int vg_scan_points(vg_ctx* ctx, float* xyz, int cap, int* n) {
 
 int vg_release_far(vg_ctx* ctx, int flags, long long* out) {
   if (!ctx || !out || (flags & ~3)) return VG_E_ARG;
+  if (flags & 1) VG_TRY(refuse_owner(ctx, "vg_release_far (compaction)"));  // node ids would move under the views
   if (!(flags & 3)) {  // nothing asked but the release: no wait unless one is pending
     VG_TRY(host_poll(ctx));
     if (!host_release_pending(ctx)) {
@@ -637,11 +662,15 @@ int vg_release_far(vg_ctx* ctx, int flags, long long* out) {
 
 int vg_checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes) {
   if (!ctx || !path) return VG_E_ARG;
+  VG_TRY(refuse_attached(ctx, "vg_checkpoint_save"));
+  VG_TRY(refuse_owner(ctx, "vg_checkpoint_save"));  // (the save compacts: node ids would move under the views)
   return checkpoint_save(ctx, path, bytes, nullptr);
 }
 
 int vg_checkpoint_load(vg_ctx* ctx, const char* path) {
   if (!ctx || !path) return VG_E_ARG;
+  VG_TRY(refuse_attached(ctx, "vg_checkpoint_load"));
+  VG_TRY(refuse_owner(ctx, "vg_checkpoint_load"));
   return checkpoint_load(ctx, path, nullptr);
 }
 
@@ -682,6 +711,7 @@ int vg_path(vg_ctx* ctx, double* out, int cap, int* n) {
 
 int vg_set_publish(vg_ctx* ctx, int flags) {
   if (!ctx || (flags & ~3)) return VG_E_ARG;
+  if (flags) VG_TRY(refuse_attached(ctx, "vg_set_publish"));  // both publications belong to a mapping context
   if ((flags & 2) && ctx->shard.world > 1) {
     ctx->err = "vg_set_publish: the plane / normal markers are not available in sharded mode";
     return VG_E_STATE;
@@ -784,6 +814,7 @@ static int need_scan(vg_ctx* ctx) {
 
 int vg_propagate(vg_ctx* ctx, const double* imu, int m, double pcl_beg_time, double pcl_end_time) {
   if (!ctx || m < 0 || (m > 0 && !imu)) return VG_E_ARG;
+  VG_TRY(refuse_fleet(ctx, "vg_propagate"));
   return stage_propagate(ctx, imu, m, pcl_beg_time, pcl_end_time);
 }
 
@@ -844,6 +875,7 @@ int vg_set_wait_policy(vg_ctx* ctx, int spin_us, int sleep_us) {
 
 int vg_profile(vg_ctx* ctx, int on) {
   if (!ctx) return VG_E_ARG;
+  if (on & 2) VG_TRY(refuse_attached(ctx, "vg_profile (per-stage bit)"));  // its P_k pass writes DevMap::stamp
   ctx->prof_on = (on & 1) != 0;
   ctx->prof_stages = (on & 2) != 0;
   ctx->prof_clock = (on & 4) != 0;

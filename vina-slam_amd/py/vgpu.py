@@ -196,6 +196,7 @@ def lib():
         L.vg_step_deskew_dev.argtypes = [P, P, P, P, P, P, ctypes.c_int, ctypes.c_double, ctypes.c_double, dp,
                                          ctypes.c_int]
         L.vg_get_state.argtypes = [P, dp]
+        L.vg_scan_points.argtypes = [P, fp, ctypes.c_int, ip]
         L.vg_get_stats.argtypes = [P, ctypes.POINTER(Stats)]
         L.vg_stats_log.argtypes = [P, ctypes.POINTER(Stats), ctypes.c_int, ip]
         L.vg_release_far.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
@@ -213,6 +214,15 @@ def lib():
             L.vg_relocalize.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(RelocParams), ctypes.c_int, dp,
                                         ctypes.POINTER(PoseScore), ip]
             L.vgx_score_ms.argtypes = [P, dp]
+        L.has_fleet = hasattr(L, "vg_fleet_create")  # a build older than the map views and the fleet (A/B runs)
+        if L.has_fleet:
+            L.vg_map_attach.argtypes = [P, P]
+            L.vg_map_detach.argtypes = [P]
+            L.vg_fleet_create.argtypes = [P, ctypes.POINTER(P), ctypes.c_int, ctypes.POINTER(P)]
+            L.vg_fleet_step_dev.argtypes = [P, ctypes.POINTER(ScanDev)]
+            L.vg_fleet_sync.argtypes = [P]
+            L.vg_fleet_destroy.argtypes = [P]
+            L.vg_fleet_destroy.restype = None
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -299,15 +309,33 @@ class Context:
             raise VgError("%s failed (%d): %s" % (what, r, lib().vg_last_error(self.h).decode()))
 
     def close(self):
+        """vg_destroy; refused (VgError -5, the context stays) while contexts are attached to
+        this one's map or a fleet steps it. An attached tracker detaches first. Close in this
+        order, explicitly: the Fleet, its trackers (or detach them), then the owner. Dropping the
+        objects instead leaves the order to the collector: __del__ swallows a refused close and
+        does not try again, so an owner collected before its trackers keeps its device memory
+        until the process ends."""
         if self.h:
-            lib().vg_destroy(self.h)
+            self._chk(lib().vg_destroy(self.h), "vg_destroy")
             self.h = None
+            self._owner = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def attach(self, owner):
+        """vg_map_attach: this context becomes a read-only view of owner's frozen map and takes
+        owner's between-scans estimator; seed() or relocalize(install=True) then places it."""
+        self._chk(lib().vg_map_attach(self.h, owner.h), "vg_map_attach")
+        self._owner = owner  # the owner outlives its views
+
+    def detach(self):
+        """vg_map_detach: this context's own (empty) map back, the context as after reset()."""
+        self._chk(lib().vg_map_detach(self.h), "vg_map_detach")
+        self._owner = None
 
     def downsample(self, xyz, inten, size):
         xyz = np.ascontiguousarray(xyz, dtype=np.float32)
@@ -387,6 +415,14 @@ class Context:
         r = self._fn_step(self.h, *p[1])
         if r != 0:
             self._chk(r, "vg_step_dev")
+
+    def scan_points(self):
+        """vg_scan_points: the last completed scan's downsampled cloud (n, 3); empty after a fleet step."""
+        n = ctypes.c_int(0)
+        self._chk(lib().vg_scan_points(self.h, None, 0, ctypes.byref(n)), "vg_scan_points")
+        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+        self._chk(lib().vg_scan_points(self.h, _f(out), n.value, ctypes.byref(n)), "vg_scan_points")
+        return out[: n.value]
 
     def state(self):
         s = np.zeros(STATE_LEN)
@@ -831,3 +867,56 @@ class Multi:
             lib().vg_multi_destroy(self.h)
             self.h = None
 
+
+class Fleet:
+    """The fleet (vg_fleet_*): B trackers attached to one owner's map, one frozen scan each per
+    step in ten launches for any B. Close order: this Fleet first, then its trackers, then the
+    owner (Context.close refuses the other orders; see its docstring). The Fleet holds references
+    to all of them, so none is collected before it."""
+
+    def __init__(self, owner, trackers):
+        self.owner = owner
+        self.trackers = list(trackers)
+        arr = (ctypes.c_void_p * len(self.trackers))(*[c.h.value for c in self.trackers])
+        self.h = ctypes.c_void_p()
+        r = lib().vg_fleet_create(owner.h, arr, len(self.trackers), ctypes.byref(self.h))
+        if r != 0:
+            self.h = None
+            raise VgError("vg_fleet_create failed (%d): %s" % (r, lib().vg_last_error(owner.h).decode()))
+        self._keep = None
+
+    def step_dev(self, scans):
+        """scans: per tracker (d_x, d_y, d_z, d_intensity, d_time or 0, n, beg, end, imu (m,7) float64),
+        or None (n < 0): the tracker sits this step out."""
+        B = len(self.trackers)
+        arr = (ScanDev * B)()
+        keep = []
+        for b, sc in enumerate(scans):
+            if sc is None:
+                arr[b] = ScanDev(None, None, None, None, None, -1, 0.0, 0.0, None, 0)
+                continue
+            x, y, z, i, t, n, beg, end, imu = sc
+            imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+            keep.append(imu)
+            arr[b] = ScanDev(x or None, y or None, z or None, i or None, t or None, n, beg, end, _d(imu), imu.shape[0])
+        r = lib().vg_fleet_step_dev(self.h, arr)
+        if r != 0:
+            raise VgError("vg_fleet_step_dev failed (%d): %s" % (
+                r, "; ".join(lib().vg_last_error(c.h).decode() for c in self.trackers)))
+
+    def sync(self):
+        r = lib().vg_fleet_sync(self.h)
+        if r != 0:
+            raise VgError("vg_fleet_sync failed (%d): %s" % (
+                r, "; ".join(lib().vg_last_error(c.h).decode() for c in self.trackers)))
+
+    def close(self):
+        if self.h:
+            lib().vg_fleet_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
