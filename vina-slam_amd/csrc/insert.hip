@@ -4,6 +4,7 @@
 //   A3  var_init / pvec_update           point_utils.cpp:3-65        (fused)
 //   A4  cut_voxel_multi -> allocate/push voxel_map.cpp:47-135, octree.cpp:151-228
 #include <cstring>
+#include <vector>
 #include "vg_map.h"
 
 namespace vg {
@@ -49,6 +50,7 @@ __global__ void __launch_bounds__(256) k_ins_prep(int n_arg, const int* __restri
     m.counters[kCntTouched] = 0;
     m.counters[kCntCreate] = 0;
     m.counters[kCntSeg] = 0;
+    m.counters[kCntSegCur] = 0;
     m.counters[kCntMisc] = 0;  // insert abort flag (child-allocation overflow)
     m.counters[kCntPlaneUpd] = 0;  // margi's per-scan branch counters (vg_stats)
     m.counters[kCntFixFull] = 0;
@@ -366,37 +368,58 @@ __device__ __forceinline__ bool ins_skip(const DevMap& m, int thread_num) {
   return g_touched(m) < thread_num || m.counters[kCntMisc] != 0;
 }
 
-// descend to a leaf; a missing child becomes a creation request (parent, octant)
+// descend to a leaf; a missing child becomes a creation request (parent, octant).
+// leaf[i]: the leaf, -1 (no root) or the request's code -2 - (parent * 8 + octant).
+// kCount: the point is counted into its bucket here — m.leaf_cnt[leaf] at an
+// existing leaf, m.creq_cnt[parent * 8 + octant] at a request (a child made by
+// alloc_parent is always a leaf) — and the bucket's first point (the first
+// arrival at the leaf, the request's CAS winner) appends its segment:
+// seg_key[s] = leaf[i]. Every segment's length is final when this launch
+// ends, so no later pass has to count (k_ins_resolve) and the offsets need no
+// ordered prefix (k_seg_offsets): k_ins_alloc_seg hands them out in any order.
+template <bool kCount>
 __global__ void __launch_bounds__(256) k_ins_descend(int n_arg, const int* __restrict__ nd, int thread_num, const double* __restrict__ pw, DevMap m,
                                                      const uint32_t* __restrict__ hslot, int* __restrict__ leaf,
-                                                     int* __restrict__ reqlist) {
+                                                     int* __restrict__ reqlist, int* __restrict__ seg_key) {
   const int n = nd ? *nd : n_arg;  // the downsampled count on the device (ds_enqueue_hashed)
   if (ins_skip(m, thread_num)) return;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t hs = hslot[i];
-    int node = hs != 0xffffffffu ? m.hval[hs] : -1;  // the point's root (registered by k_ins_roots_alloc)
-    leaf[i] = node;
-    if (node < 0) continue;
-    V3 w = v3(pw[3 * i], pw[3 * i + 1], pw[3 * i + 2]);
-    for (int d = 0; d < 8; d++) {
-      const NodeHdr& h = m.hdr[node];
-      if (h.octo == 0) break;
-      int o = octant(w, h.center);
-      int c = h.child[o];
-      if (c < 0) {
-        // request (parent, octant); the first requester of a parent registers it
-        if (atomicCAS(&m.cfirst[(size_t)node * 8 + o], 0x7f7f7f7f, -5) == 0x7f7f7f7f) {
-          if (atomicExch(&m.nscr[(size_t)node * 4 + 1], -7) != -7) {
-            int pos = atomicAdd(&m.counters[kCntCreate], 1);
-            reqlist[pos] = node;
-          }
-        }
-        node = -2 - (node * 8 + o);
-        break;
-      }
-      node = c;
+  for (int base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {
+    const int i = base + threadIdx.x;
+    int node = -1;
+    bool first = false;
+    if (i < n) {
+      const uint32_t hs = hslot[i];
+      node = hs != 0xffffffffu ? m.hval[hs] : -1;  // the point's root (registered by k_ins_roots_alloc)
     }
-    leaf[i] = node;
+    if (node >= 0) {
+      V3 w = v3(pw[3 * i], pw[3 * i + 1], pw[3 * i + 2]);
+      for (int d = 0; d < 8; d++) {
+        const NodeHdr& h = m.hdr[node];
+        if (h.octo == 0) break;
+        int o = octant(w, h.center);
+        int c = h.child[o];
+        if (c < 0) {
+          // request (parent, octant); the first requester of a parent registers it
+          if (atomicCAS(&m.cfirst[(size_t)node * 8 + o], 0x7f7f7f7f, -5) == 0x7f7f7f7f) {
+            first = true;
+            if (atomicExch(&m.nscr[(size_t)node * 4 + 1], -7) != -7) {
+              int pos = atomicAdd(&m.counters[kCntCreate], 1);
+              reqlist[pos] = node;
+            }
+          }
+          if (kCount) atomicAdd(&m.creq_cnt[(size_t)node * 8 + o], 1);
+          node = -2 - (node * 8 + o);
+          break;
+        }
+        node = c;
+      }
+      if (kCount && node >= 0) first = atomicAdd(&m.leaf_cnt[node], 1) == 0;
+    }
+    if (i < n) leaf[i] = node;
+    if (kCount) {
+      const int s = wave_append(&m.counters[kCntSeg], first ? 1 : 0);
+      if (first) seg_key[s] = node;
+    }
   }
 }
 
@@ -503,6 +526,18 @@ struct RcBeginArg {
   int* slot_of;
   int* rc;
 };
+// a segment's bucket count: per leaf, or per child request (k_ins_descend<true>)
+__device__ __forceinline__ int* seg_counter(const DevMap& m, int key) {
+  return key >= 0 ? &m.leaf_cnt[key] : &m.creq_cnt[-2 - key];
+}
+// kCur: the counted descent's hand-off — seg_leaf[s] is the segment's key (a
+// leaf, or a request whose child the allocation has made by now) and seg_off
+// holds (offset, length) pairs (k_ins_alloc_seg); else seg_off[s], seg_off[s + 1]
+// bracket the segment (k_seg_offsets).
+// kPipe: the records of a long segment's next 64 points are loaded into
+// registers ahead of the current block's serial sums (the sums' order is the
+// same), and a mid-size segment is ranked from a copy of its indices in LDS.
+template <bool kCur, bool kPipe>
 __global__ void __launch_bounds__(64 * kPushWaves, 4) k_push_window(const int* __restrict__ seg_leaf,
                                                                  const int* __restrict__ seg_off,
                                                                  const int* __restrict__ order,
@@ -523,8 +558,25 @@ __global__ void __launch_bounds__(64 * kPushWaves, 4) k_push_window(const int* _
   const int nseg = m.counters[kCntSeg];
   const int gsz = (int)gridDim.x - (has_rb ? 1 : 0);
   for (int sg = blockIdx.x * kPushWaves + wv; sg < nseg; sg += gsz * kPushWaves) {
-    const int j0 = seg_off[sg], L = seg_off[sg + 1] - j0;
-    const int leaf = seg_leaf[sg];
+    int j0, L, leaf;
+    int* bucket;  // the bucket's count, back to zero at the end (the bucketing invariant)
+    if (kCur) {
+      const int2 ol = reinterpret_cast<const int2*>(seg_off)[sg];
+      const int key = seg_leaf[sg];
+      j0 = ol.x;
+      L = ol.y;
+      bucket = seg_counter(m, key);
+      leaf = key >= 0 ? key : m.hdr[(-2 - key) >> 3].child[(-2 - key) & 7];
+      if (leaf < 0) {  // the child was not made (node pool full, kCntErr): nothing to push into
+        if (lane == 0) *bucket = 0;
+        continue;
+      }
+    } else {
+      j0 = seg_off[sg];
+      L = seg_off[sg + 1] - j0;
+      leaf = seg_leaf[sg];
+      bucket = &m.leaf_cnt[leaf];
+    }
     // the leaf's points in index order (the reference's push order): up to 64
     // sorted across the lanes (bitonic by xor shuffles), longer segments ranked
     // into order2
@@ -538,6 +590,21 @@ __global__ void __launch_bounds__(64 * kPushWaves, 4) k_push_window(const int* _
           const bool up = (lane & k) == 0, low = (lane & j) == 0;
           mine = (low == up) ? min(mine, other) : max(mine, other);
         }
+    } else if (kPipe && L <= kPwRankMax) {  // a few hundred points: each ranked against the others, staged in LDS
+      int* idx = reinterpret_cast<int*>(&E[wv][0][0]);  // free until the records are filled
+      for (int e = lane; e < L; e += 64) idx[e] = order[j0 + e];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      for (int e = lane; e < L; e += 64) {
+        const int x = idx[e];
+        int r = 0;
+        for (int t = 0; t < L; t++) r += idx[t] < x ? 1 : 0;
+        order2[j0 + r] = x;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     } else if (L <= kPwRankMax) {  // a few hundred points: each ranked against the (L1-resident) others
       for (int e = lane; e < L; e += 64) {
         const int x = order[j0 + e];
@@ -621,23 +688,53 @@ __global__ void __launch_bounds__(64 * kPushWaves, 4) k_push_window(const int* _
                     : role < 18 ? (role < 15 ? &add->P[role - 9] : &add->v[role - 15])
                                 : &m.cov_add[(size_t)leaf * kCovN + role - 18];
     double acc = acc_p ? *acc_p : 0.0;
-    for (int base = 0; base < L; base += 64) {
-      const int e = base + lane;
-      const bool valid = e < L;
-      if (valid) {
-        const int i = L <= 64 ? mine : order2[j0 + e];
-        const size_t b = (size_t)slot * m.cap_wp + i;
-        fill_record(E[wv][lane], ld_v3(&m.wp_pnt[b * 3]), v3(pw[3 * i], pw[3 * i + 1], pw[3 * i + 2]),
-                    ld_m3(&m.wp_var[b * 9]));
-        if (listed) m.wp_leaf[b] = leaf;
-      }
-      const int nb = min(64, L - base);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (kPipe && L > 64) {
+      // the next block's record loads (15 doubles a lane, each dependent on
+      // order2) are in flight while this block's 64 ordered adds run
+      V3 q, p;
+      M3 V;
+      auto load = [&](int base) {
+        const int e = base + lane;
+        if (e < L) {
+          const int i = order2[j0 + e];
+          const size_t b = (size_t)slot * m.cap_wp + i;
+          q = ld_v3(&m.wp_pnt[b * 3]);
+          p = v3(pw[3 * i], pw[3 * i + 1], pw[3 * i + 2]);
+          V = ld_m3(&m.wp_var[b * 9]);
+          if (listed) m.wp_leaf[b] = leaf;
+        }
+      };
+      load(0);
+      for (int base = 0; base < L; base += 64) {
+        if (base + lane < L) fill_record(E[wv][lane], q, p, V);
+        const int nb = min(64, L - base);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        load(base + 64);
 #pragma unroll 8
-      for (int k = 0; k < nb; k++) acc += role_inc(E[wv][k], ri);  // unrolled: the LDS reads run ahead of the sum
-      __builtin_amdgcn_wave_barrier();
+        for (int k = 0; k < nb; k++) acc += role_inc(E[wv][k], ri);
+        __builtin_amdgcn_wave_barrier();
+      }
+    } else {
+      for (int base = 0; base < L; base += 64) {
+        const int e = base + lane;
+        const bool valid = e < L;
+        if (valid) {
+          const int i = L <= 64 ? mine : order2[j0 + e];
+          const size_t b = (size_t)slot * m.cap_wp + i;
+          fill_record(E[wv][lane], ld_v3(&m.wp_pnt[b * 3]), v3(pw[3 * i], pw[3 * i + 1], pw[3 * i + 2]),
+                      ld_m3(&m.wp_var[b * 9]));
+          if (listed) m.wp_leaf[b] = leaf;
+        }
+        const int nb = min(64, L - base);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 8
+        for (int k = 0; k < nb; k++) acc += role_inc(E[wv][k], ri);  // unrolled: the LDS reads run ahead of the sum
+        __builtin_amdgcn_wave_barrier();
+      }
     }
     if (acc_p) *acc_p = acc;
     if (lane == 0) {
@@ -645,7 +742,7 @@ __global__ void __launch_bounds__(64 * kPushWaves, 4) k_push_window(const int* _
       add->N += L;
       m.hdr[leaf].has_sw = 1;
       m.hdr[leaf].isexist = 1;
-      m.leaf_cnt[leaf] = 0;  // bucketing invariant: zero between inserts
+      *bucket = 0;  // bucketing invariant: zero between inserts
     }
   }
 }
@@ -675,10 +772,8 @@ __device__ void lds_bitonic(T* a, int n) {
 // records zeroed. More than kInsAllocCap parents sets the abort flag and the
 // host replays the allocation on the host-sized path.
 constexpr int kInsAllocCap = 4096;
-__global__ void __launch_bounds__(1024) k_ins_alloc(int thread_num, DevMap m, const int* __restrict__ reqlist,
-                                                    int cap) {
-  __shared__ int sp[kInsAllocCap];
-  __shared__ int s_w[17];
+__device__ __forceinline__ void ins_alloc_block(int thread_num, DevMap& m, const int* __restrict__ reqlist, int cap,
+                                                int* sp, int* s_w) {
   if (g_touched(m) < thread_num) return;
   const int np = m.counters[kCntCreate];
   if (np == 0) return;
@@ -707,6 +802,60 @@ __global__ void __launch_bounds__(1024) k_ins_alloc(int thread_num, DevMap m, co
   __syncthreads();
   if (threadIdx.x == 0) m.counters[kCntNodes] = base + carry;
 }
+__global__ void __launch_bounds__(1024) k_ins_alloc(int thread_num, DevMap m, const int* __restrict__ reqlist,
+                                                    int cap) {
+  __shared__ int sp[kInsAllocCap];
+  __shared__ int s_w[17];
+  ins_alloc_block(thread_num, m, reqlist, cap, sp, s_w);
+}
+
+// The child allocation (workgroup 0, as k_ins_alloc) and, beside it, the
+// segment allocation of the counted descent (the other workgroups): a
+// segment's place in the bucketed point order is a wave-aggregated atomicAdd
+// of its length on one cursor — any order will do, k_push_window treats every
+// leaf on its own. seg_ol[s] = (offset, length); the bucket's count becomes
+// its fill cursor (k_ins_scatter_cur adds from there), so it holds offset +
+// length after the scatter and k_push_window returns it to zero. The two
+// halves share nothing: the segments need the counts only, not the children's
+// ids (k_push_window resolves a request's child), and a child-allocation
+// overflow (kCntMisc, raised in this launch) leaves the segments valid for
+// map_insert_replay's tail.
+constexpr int kSegAllocBlocks = 8;
+__global__ void __launch_bounds__(1024) k_ins_alloc_seg(int thread_num, DevMap m, const int* __restrict__ reqlist,
+                                                        int cap, const int* __restrict__ seg_key,
+                                                        int2* __restrict__ seg_ol) {
+  __shared__ int sp[kInsAllocCap];
+  __shared__ int s_w[17];
+  if (blockIdx.x == 0) {
+    ins_alloc_block(thread_num, m, reqlist, cap, sp, s_w);
+    return;
+  }
+  if (g_touched(m) < thread_num) return;  // (the descent did not run: no segments)
+  const int ns = m.counters[kCntSeg];
+  for (int base = ((int)blockIdx.x - 1) * (int)blockDim.x; base < ns; base += ((int)gridDim.x - 1) * (int)blockDim.x) {
+    const int s = base + threadIdx.x;
+    int* c = s < ns ? seg_counter(m, seg_key[s]) : nullptr;
+    const int len = c ? *c : 0;
+    const int off = wave_append(&m.counters[kCntSegCur], len);
+    if (c) {
+      seg_ol[s] = make_int2(off, len);
+      *c = off;
+    }
+  }
+}
+
+// every point into its segment (arbitrary order inside it), counted descent:
+// the bucket's counter is the segment's fill cursor (k_ins_alloc_seg)
+__global__ void __launch_bounds__(256) k_ins_scatter_cur(int n_arg, const int* __restrict__ nd, int thread_num, DevMap m,
+                                                         const int* __restrict__ leaf, int* __restrict__ order) {
+  const int n = nd ? *nd : n_arg;  // the downsampled count on the device (ds_enqueue_hashed)
+  if (ins_skip(m, thread_num)) return;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int l = leaf[i];
+    if (l == -1) continue;
+    order[atomicAdd(seg_counter(m, l), 1)] = i;
+  }
+}
 
 // leaves -> sorted (leaf, order) keys -> pushes of one insert
 static int insert_tail(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_num, const int* nd = nullptr) {
@@ -719,10 +868,16 @@ static int insert_tail(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_nu
   int* seg_off = reinterpret_cast<int*>(w.v0);
   int* order = reinterpret_cast<int*>(w.k0);
   int* order2 = reinterpret_cast<int*>(w.k1);
-  // leaves -> per-leaf buckets (no sort: the order between leaves is free)
-  k_ins_resolve<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, w.pw, m, w.leaf, seg_leaf);
-  k_seg_offsets<<<1, 1024, 0, s>>>(thread_num, m, seg_leaf, seg_off);
-  k_ins_scatter<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, m, w.leaf, seg_off, order);
+  const bool cur = ctx->ins_count;
+  if (cur) {
+    // counted descent: the segments and their offsets exist (k_ins_descend<true>, k_ins_alloc_seg)
+    k_ins_scatter_cur<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, m, w.leaf, order);
+  } else {
+    // leaves -> per-leaf buckets (no sort: the order between leaves is free)
+    k_ins_resolve<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, w.pw, m, w.leaf, seg_leaf);
+    k_seg_offsets<<<1, 1024, 0, s>>>(thread_num, m, seg_leaf, seg_off);
+    k_ins_scatter<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, m, w.leaf, seg_off, order);
+  }
   // ~one wave per leaf segment (the count stays on the device); plus the
   // recut's head when the recut follows in the same graph (ctx->rc_begin_wa)
   RcBeginArg rb;
@@ -739,8 +894,10 @@ static int insert_tail(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_nu
     ctx->rc_begin_wa = nullptr;
     ctx->rc_begun = true;
   }
-  k_push_window<<<gseg + (has_rb ? 1 : 0), 64 * kPushWaves, 0, s>>>(seg_leaf, seg_off, order, order2, mp, slot, m, w.pw,
-                                                                     thread_num, rb, has_rb ? 1 : 0);
+  auto push = cur ? (ctx->push_pipe ? k_push_window<true, true> : k_push_window<true, false>)
+                  : (ctx->push_pipe ? k_push_window<false, true> : k_push_window<false, false>);
+  push<<<gseg + (has_rb ? 1 : 0), 64 * kPushWaves, 0, s>>>(seg_leaf, seg_off, order, order2, mp, slot, m, w.pw, thread_num,
+                                                            rb, has_rb ? 1 : 0);
   VG_HIP(hipGetLastError());
   return VG_OK;
 }
@@ -789,9 +946,17 @@ int map_insert(vg_ctx* ctx, const MP& mp, int slot, int n, int epoch, int thread
   if (sharded(ctx)) {  // the thread_num quirk counts distinct roots over all shards
     VG_TRY(shard_allreduce(ctx, m.counters + kCntTouched, m.counters + kCntGTouched, 1, 1, 1));
   }
-  k_ins_descend<<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, w.pw, m, w.u0, w.leaf, w.list2);
   const int ins_cap = (ctx->dbg_ins_cap >= 0 && ctx->dbg_ins_cap < kInsAllocCap) ? ctx->dbg_ins_cap : kInsAllocCap;
-  k_ins_alloc<<<1, 1024, 0, s>>>(thread_num, m, w.list2, ins_cap);
+  if (ctx->ins_count) {  // prep -> roots -> descend (+ counts) -> alloc || segment allocation -> scatter -> push
+    k_ins_descend<true><<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, w.pw, m, w.u0, w.leaf,
+                                                                             w.list2, w.list1);
+    k_ins_alloc_seg<<<1 + kSegAllocBlocks, 1024, 0, s>>>(thread_num, m, w.list2, ins_cap, w.list1,
+                                                         reinterpret_cast<int2*>(w.v0));
+  } else {
+    k_ins_descend<false><<<g * (kBlock / kSpreadBlock), kSpreadBlock, 0, s>>>(n, nd, thread_num, w.pw, m, w.u0, w.leaf,
+                                                                              w.list2, nullptr);
+    k_ins_alloc<<<1, 1024, 0, s>>>(thread_num, m, w.list2, ins_cap);
+  }
   return insert_tail(ctx, mp, slot, n, thread_num, nd);
 }
 
@@ -802,10 +967,39 @@ int map_insert_replay(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_num
   VG_TRY(read_counters(ctx));
   const int np = ctx->h_pinned[kCntCreate];
   VG_HIP(hipMemsetAsync(m.counters + kCntMisc, 0, sizeof(int), s));
-  VG_HIP(hipMemsetAsync(m.counters + kCntSeg, 0, sizeof(int), s));
+  // (the counted descent's segments and request counts stand: its tail is the scatter and the push)
+  if (!ctx->ins_count) VG_HIP(hipMemsetAsync(m.counters + kCntSeg, 0, sizeof(int), s));
   int created = 0;
   VG_TRY(alloc_children(ctx, ctx->wk.list2, np, nullptr, 0, false, &created));
   return insert_tail(ctx, mp, slot, n, thread_num);
+}
+
+// test hook (vgx_insert_segments): the last insert's segments while its work
+// buffers still stand (right after vg_cut_voxel_multi) — per segment its key
+// (a leaf id; with the counted descent a child request stays -2 - (parent * 8
+// + octant)) and its length; info = {segments, roots touched, parents with
+// child requests, abort flag}. Segments past cap are not written.
+int map_insert_segments(vg_ctx* ctx, int* key, int* len, int cap, int* info) {
+  DevMap& m = ctx->map;
+  Work& w = ctx->wk;
+  hipStream_t s = ctx->stream;
+  int hc[kCntN];
+  VG_HIP(hipMemcpyAsync(hc, m.counters, sizeof(hc), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipStreamSynchronize(s));
+  const int ns = hc[kCntSeg];
+  info[0] = ns;
+  info[1] = hc[kCntTouched];
+  info[2] = hc[kCntCreate];
+  info[3] = hc[kCntMisc];
+  const int k = ns < cap ? ns : cap;
+  if (k <= 0) return VG_OK;
+  std::vector<int> off((size_t)2 * k + 2);
+  VG_HIP(hipMemcpyAsync(key, w.list1, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(off.data(), w.v0, (ctx->ins_count ? (size_t)2 * k : (size_t)k + 1) * sizeof(int),
+                        hipMemcpyDeviceToHost, s));
+  VG_HIP(hipStreamSynchronize(s));
+  for (int q = 0; q < k; q++) len[q] = ctx->ins_count ? off[2 * q + 1] : off[q + 1] - off[q];
+  return VG_OK;
 }
 
 }  // namespace vg

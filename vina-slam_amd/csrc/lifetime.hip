@@ -368,6 +368,7 @@ int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, lo
           {m.dbox, 6 * 8, -1},                  {m.pcrs, (size_t)W * sizeof(Clu), 0}, {m.nscr, 16, 0xff},
           {m.pend, 8, -1},                      {m.cfirst, 32, 0x7f},              {m.leaf_cnt, 4, 0},
           {m.leaf_seg, 4, -1},                  {m.lseg, (size_t)W * 8, 0},        {m.stamp, 4, 0},
+          {m.creq_cnt, 32, 0},
       };
       for (const Arr& a : arrs) {
         const int w = (int)(a.rec / 4);

@@ -47,6 +47,7 @@ int map_alloc(vg_ctx* ctx) {
   good &= ok(m.in_slide = ctx->arena.take<uint8_t>(cn));
   good &= ok(m.leaf_cnt = ctx->arena.take<int>(cn));
   good &= ok(m.leaf_seg = ctx->arena.take<int>(cn));
+  good &= ok(m.creq_cnt = ctx->arena.take<int>(cn * 8));
   good &= ok(m.fix_pnt = ctx->arena.take<double>((size_t)m.cap_fix * 3));
   good &= ok(m.fix_var = ctx->arena.take<double>((size_t)m.cap_fix * 9));
   good &= ok(m.wp_pnt = ctx->arena.take<double>(cw * W * 3));
@@ -146,6 +147,7 @@ int map_reset(vg_ctx* ctx) {
   VG_HIP(hipMemsetAsync(m.in_slide, 0, m.cap_nodes, s));
   VG_HIP(hipMemsetAsync(m.leaf_cnt, 0, (size_t)m.cap_nodes * sizeof(int), s));
   VG_HIP(hipMemsetAsync(m.cfirst, 0x7f, (size_t)m.cap_nodes * 8 * sizeof(int), s));
+  VG_HIP(hipMemsetAsync(m.creq_cnt, 0, (size_t)m.cap_nodes * 8 * sizeof(int), s));
   VG_HIP(hipMemsetAsync(m.nscr, 0xff, (size_t)m.cap_nodes * 4 * sizeof(int), s));
   VG_HIP(hipStreamSynchronize(s));
   return ds_reset(ctx);  // the pipeline downsample's voxel table

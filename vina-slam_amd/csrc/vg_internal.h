@@ -157,6 +157,7 @@ struct DevMap {
   uint8_t* in_slide = nullptr;
   int* leaf_cnt = nullptr;     // insert bucketing: points of this scan per leaf (0 between inserts)
   int* leaf_seg = nullptr;     // insert bucketing: the leaf's segment
+  int* creq_cnt = nullptr;     // insert bucketing: points of this scan per child request (parent * 8 + octant; 0 between inserts)
   double* fix_pnt = nullptr;   // point_fix arena: pnt (world) 3, var 6
   double* fix_var = nullptr;
   double* wp_pnt = nullptr;    // window points per physical slot: body pnt
@@ -178,13 +179,14 @@ struct DevMap {
   int* wpn = nullptr;          // window points per physical slot (written by the insert, read by k_make_win)
 };
 enum {
-  kCntNodes = 0, kCntFix = 1, kCntSlide = 2, kCntNew = 3, kCntTouched = 4, kCntWork = 5, kCntNext = 6,
+  kCntNodes = 0, kCntFix = 1, kCntSlide = 2, kCntNew = 3, kCntTouched = 4, kCntSegCur = 5, kCntNext = 6,
   kCntSub = 7, kCntEvents = 8, kCntFactors = 9, kCntCreate = 10, kCntErr = 11, kCntLeaves = 12, kCntMisc = 13, kCntSeg = 14, kCntRoots = 15,
   kCntGTouched = 16, kCntGSlide = 17,  // all-reduced copies (sharded mode) for the thread_num quirks
   kCntPlaneUpd = 18, kCntFixFull = 19,  // margi: plane_update calls, leaves with pcr_fix.N >= max_points
   kCntSlideBase = 20,                   // insert: surf_map_slide size before the scan's roots
   kCntNds = 21,                         // insert: the downsampled points it took (N_ds of the scan)
   kCntN = 22
+  // kCntSegCur: the insert's segment cursor (the next free entry of the bucketed point order)
 };
 
 // per-scan work buffers
@@ -530,6 +532,9 @@ struct vg_ctx {
   long prof_runs = 0;
   int rc_total = 0, rc_thread_num = 0;  // the last recut's window point total / thread_num (its resume)
   bool prof_stages = false;  // per-stage events (vg_profile bit 1)
+  bool ins_count = true;     // vgx_debug 38: the insert counts its buckets in the descent (0: k_ins_resolve + k_seg_offsets)
+  bool push_pipe = false;    // vgx_debug 39: 1 = k_push_window loads a block's records ahead of the previous block's sums and ranks
+                             // mid-size segments from LDS (bit-identical; measured 29.0 -> 30.6 us, so off: DESIGN.md section 6)
   bool roots_lb = true;      // root registration in one look-back launch (vgx_debug 16: 0 = two launches)
   bool ba_graph2 = true;     // the first two LM iterations as one graph (vgx_debug 17: 0 = one graph each)
   bool margi_batch = true;    // vgx_debug 24: k_margi_leaf reads a leaf's frame clusters four at a time (r04k +0.4 %)
@@ -743,6 +748,7 @@ struct InsPre {
 int map_insert(vg_ctx* ctx, const MP& mp, int slot, int n, int epoch, int thread_num, const PushArg* push = nullptr,
                const InsPre* pre = nullptr, const int* nd = nullptr);
 int map_insert_replay(vg_ctx* ctx, const MP& mp, int slot, int n, int thread_num);
+int map_insert_segments(vg_ctx* ctx, int* key, int* len, int cap, int* info);  // test hook (vgx_insert_segments)
 // recut.hip
 constexpr int kNeedInsertReplay = 1;  // map_recut: the insert overflowed k_ins_alloc, replay it first
 int map_recut(vg_ctx* ctx, const MP& mp, const WinArg& wa, int thread_num, int* n_factors, bool replay = false,

@@ -1014,6 +1014,14 @@ extern "C" int vgx_debug(vg_ctx* ctx, int key, int value) {
     ctx->ba_graph2 = value != 0;
     return VG_OK;
   }
+  if (key == 38) {  // 0: the insert buckets by k_ins_resolve + k_seg_offsets instead of counting in the descent
+    ctx->ins_count = value != 0;
+    return VG_OK;
+  }
+  if (key == 39) {  // 1: k_push_window loads each block of records ahead of the previous block's sums (default 0)
+    ctx->push_pipe = value != 0;
+    return VG_OK;
+  }
   if (key == 16) {  // 0: root registration as k_ins_flags + k_ins_roots_alloc
     ctx->roots_lb = value != 0;
     return VG_OK;
@@ -1119,6 +1127,15 @@ extern "C" int vgx_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, 
   if (!ctx || !n || cap < 0 || (cap > 0 && (!key || !jour || !flags || !nodes || !nfix))) return VG_E_ARG;
   VG_TRY(host_sync(ctx));
   return map_roots(ctx, key, jour, flags, nodes, nfix, cap, n);
+}
+
+// Test-only: the last insert's leaf segments (insert.hip map_insert_segments),
+// read right after vg_cut_voxel_multi: key[s] (leaf id, or a child request
+// -2 - (parent * 8 + octant)), len[s], info[4] = {segments, roots touched,
+// parents with requests, abort flag}.
+extern "C" int vgx_insert_segments(vg_ctx* ctx, int* key, int* len, int cap, int* info) {
+  if (!ctx || !info || cap < 0 || (cap > 0 && (!key || !len))) return VG_E_ARG;
+  return map_insert_segments(ctx, key, len, cap, info);
 }
 
 // Test-only: the per-scan pipeline's hashed downsample (ds_enqueue_hashed,
