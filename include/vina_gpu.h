@@ -391,6 +391,92 @@ int vg_reloc_grid(const vg_reloc_params* prm, double* out, int cap, int* count);
 int vg_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess_pose,
                   const vg_reloc_params* prm, int install, double* out_pose, vg_pose_score* out_score, int* ok);
 
+/* ---- Ray-casting the map ------------------------------------------------------
+ * Rays through the hashed root voxels and their octrees to the first plane they
+ * meet: the expected range of the map from a pose, and a scan checked against
+ * it. Reads the map only (the DevMap the IEKF reads) and writes nothing.
+ *
+ * A ray is an origin o, a direction d (world frame; normalised on the device)
+ * and an interval (t_min, t_max] (t_min < 0 counts as 0). A leaf the descent
+ * can reach is a candidate when it holds a plane (n, c), |n.d| >= min_cos, and
+ * h = o + t d with t = n.(c - o) / (n.d) has t in the interval and lies in the
+ * leaf's cube (voxel centre +- 2 quater_length per axis, faces included). The
+ * hit is the candidate of smallest t; equal t goes to the lower node id. */
+typedef struct vg_ray_params {
+  double t_min, t_max;   /* t_max <= 0: 100 m */
+  double min_cos;        /* planes with |n.d| below it are passed through; <= 0: 0.05 */
+  int    max_steps;      /* root cells + octree nodes a ray may visit; <= 0: 4096 */
+  int    pad;
+  double reserved[4];
+} vg_ray_params;
+typedef struct vg_ray_hit {   /* 64 bytes, no implicit padding */
+  double  range;              /* t of the hit; 0 where there is none */
+  double  var;                /* variance of range from the plane's covariance: J S J^T / (n.d)^2 with
+                                 J = [h - c, -n] and S the plane's 6 x 6 (the first term of match()'s gate) */
+  double  normal[3];          /* the plane's normal as stored */
+  double  ndotd;              /* signed */
+  int32_t leaf;               /* node id, -1: none */
+  int32_t flags;              /* bit 0 hit, 1 truncated, 2 crossed an occupied leaf without a plane,
+                                 3 left the key range, 4 invalid ray (zero or non-finite direction / origin) */
+  double  reserved;
+} vg_ray_hit;
+#define VG_RAY_HIT 1
+#define VG_RAY_TRUNCATED 2
+#define VG_RAY_OCCUPIED 4
+#define VG_RAY_LEFT_RANGE 8
+#define VG_RAY_INVALID 16
+/* origins: n_origins x 3 doubles, n_origins = 1 (shared by all rays) or n.
+ * dirs: n x 3 doubles. prm: NULL for the defaults. out: n records.
+ * A ray that visits max_steps cells and nodes ends as a miss with bit 1; one
+ * that walks out of the packed key range (|cell index| >= 2^20) ends with bit
+ * 3. Bit 2: before it ended the ray crossed a leaf that holds points but no
+ * plane (occupied, surface unknown). A ray's record depends on the ray and the
+ * map alone: the same bits alone or at any position of any batch. n is walked
+ * in slabs of max_points_per_scan rays; the staging is allocated on the first
+ * call. n == 0 is fine; an empty map gives all-miss records. A NULL pointer,
+ * n < 0 or n_origins not in {1, n}: VG_E_ARG. Completes outstanding work first;
+ * between scans or inside an open stage-level scan; with mapping on or off; on
+ * an attached tracker (the owner's map) and on a fleet's tracker. Unsharded
+ * contexts only (VG_E_STATE with world > 1). */
+int vg_raycast(vg_ctx* ctx, const double* origins, int n_origins, const double* dirs, int n,
+               const vg_ray_params* prm, vg_ray_hit* out);
+
+/* Scan-vs-map change detection: every point of a scan against the range the map
+ * expects along its beam. Per point x (LiDAR frame, as vg_score_poses), at the
+ * pose (R, p): the sensor origin o = p + R ext_t, w = R (ext_R x + ext_t) + p,
+ * r = |w - o|, and one ray from o along w - o cast to min(r + gate_max,
+ * ray.t_max), gate_max = the gate below at |n.d| = min_cos with var = 0, plus
+ * 1 m. With m the ray's hit and c = |m.ndotd|:
+ *   gate^2 = gate_sigma^2 (m.var + dept_err^2 + (r sin(beam_err deg))^2 (1 - c^2) / c^2),
+ *   floored at gate_floor^2 (dept_err, beam_err: the configuration's, as calcBodyVar uses them);
+ *   no hit: UNKNOWN; |m.range - r| <= gate: CONSISTENT; m.range > r + gate:
+ *   APPEARED (something stands in front of the mapped surface); m.range <
+ *   r - gate: VANISHED (the beam passed through a mapped plane). */
+enum { VG_DIFF_UNKNOWN = 0, VG_DIFF_CONSISTENT = 1, VG_DIFF_APPEARED = 2, VG_DIFF_VANISHED = 3 };
+typedef struct vg_diff_params {
+  vg_ray_params ray;
+  double gate_sigma;     /* <= 0: 3 */
+  double gate_floor;     /* metres, default 0 */
+  double reserved[4];
+} vg_diff_params;
+typedef struct vg_diff_point {   /* 32 bytes */
+  int32_t cls, leaf;             /* VG_DIFF_*; the hit's node id, -1: none */
+  double  r_meas, r_map, gate;   /* r; the hit's range and the gate, 0 where there is no hit */
+} vg_diff_point;
+typedef struct vg_diff_summary {
+  int32_t n[4];                  /* points per class, indexed by VG_DIFF_* */
+  int32_t n_truncated, n_occupied_unknown;  /* rays with bit 1; rays with bit 2 */
+  double  sum_abs_consistent;    /* sum |m.range - r| over the CONSISTENT points, one fixed-order reduction */
+  double  reserved[3];
+} vg_diff_summary;
+/* xyz: n x 3 floats, n <= max_points_per_scan. pose12: [R row-major 9, p 3], or
+ * NULL for the context's current state. prm: NULL for the defaults. per_point
+ * (may be NULL): n records. A point's record and the counts do not depend on
+ * its position in the batch. NULL xyz (n > 0) or out, n < 0, n too large:
+ * VG_E_ARG. Legal where vg_raycast is. */
+int vg_scan_diff(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* prm,
+                 vg_diff_point* per_point, vg_diff_summary* out);
+
 /* ---- Map views: many sensors in one frozen map ------------------------------
  * vg_map_attach makes `tracker` a read-only view of `owner`'s map: every kernel
  * of the tracker that reads the map (the IEKF, vg_score_poses, vg_relocalize,

@@ -126,6 +126,20 @@ class LioCore {
     check(vg_relocalize(ctx_, xyz, n, guess_pose, &prm, install ? 1 : 0, out_pose, score, &ok), "vg_relocalize");
     return ok != 0;
   }
+  // ray-casting the map (vina_gpu.h): n rays -> n records; n_origins 1 (shared) or n; prm may be null
+  std::vector<vg_ray_hit> raycast(const double* origins, int n_origins, const double* dirs, int n,
+                                  const vg_ray_params* prm = nullptr) {
+    std::vector<vg_ray_hit> out((size_t)(n > 0 ? n : 0));
+    check(vg_raycast(ctx_, origins, n_origins, dirs, n, prm, out.data()), "vg_raycast");
+    return out;
+  }
+  // a scan against the map's expected ranges; pose12 null: the current state; per_point may be null
+  vg_diff_summary scan_diff(const float* xyz, int n, const double* pose12 = nullptr,
+                            const vg_diff_params* prm = nullptr, vg_diff_point* per_point = nullptr) {
+    vg_diff_summary out;
+    check(vg_scan_diff(ctx_, xyz, n, pose12, prm, per_point, &out), "vg_scan_diff");
+    return out;
+  }
   // map views (vina_gpu.h "Map views"): this context reads owner's frozen map. The owner
   // must outlive its views: destroy (or detach) the trackers first
   void attach(LioCore& owner) { check(vg_map_attach(ctx_, owner.ctx_), "vg_map_attach"); }

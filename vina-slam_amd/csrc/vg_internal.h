@@ -397,6 +397,16 @@ struct ScoreBufs {
   int n = 0;                  // points of the cloud in xyz
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the last vg_score_poses call's kernels (vgx_score_ms)
 };
+// vg_raycast / vg_scan_diff staging (raycast.hip): one slab of cap =
+// max_points_per_scan rays, allocated on first use, freed by vg_destroy (ray_free)
+struct RayBufs {
+  double* org = nullptr;   // cap x 3 origins (vg_scan_diff: the points' |m.range - r| terms)
+  double* dir = nullptr;   // cap x 3 directions (vg_scan_diff: the cloud, n x 3 floats)
+  void* out = nullptr;     // cap vg_ray_hit records (vg_scan_diff: vg_diff_point records)
+  void* sum = nullptr;     // one vg_diff_summary
+  int cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last call's kernels (vgx_ray_ms)
+};
 // window view for the map kernels, built on the device from DState::xs
 struct WinArg {
   int mp[kMaxWin];      // mp[] ring (octree.cpp:75)
@@ -524,6 +534,7 @@ struct vg_ctx {
   vg::DevMap own_map;         // an attached tracker's own map
   void* fleet = nullptr;      // a fleet's tracker (vg_fleet_create): stepped only through the fleet
   vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
+  vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
   vg_stats stats;
   void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
   // stage timing with HIP events on the context stream (vg_profile)
@@ -902,6 +913,19 @@ int score_poses_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const do
 // the IEKF's 34 sums (HTH, HTz, nnt, matches) of the uploaded cloud at one pose
 int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const double* pose_var, double* out34);
 void score_free(vg_ctx* ctx);
+// raycast.hip: rays through the map to the first plane (host arrays in, host
+// records out; synchronous on the context stream, which the caller drained)
+int raycast_dev(vg_ctx* ctx, const MP& mp, const double* origins, int n_origins, const double* dirs, int n,
+                const vg_ray_params* prm, vg_ray_hit* out);
+// a scan's points against the map's expected range along their beams, at pose12
+int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
+                  const vg_diff_params* prm, vg_diff_point* per_point, vg_diff_summary* out);
+void ray_free(vg_ctx* ctx);
+// raycast_host.cpp: the two calls behind the C-ABI
+int host_raycast(vg_ctx* ctx, const double* origins, int n_origins, const double* dirs, int n,
+                 const vg_ray_params* prm, vg_ray_hit* out);
+int host_scan_diff(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* prm,
+                   vg_diff_point* per_point, vg_diff_summary* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

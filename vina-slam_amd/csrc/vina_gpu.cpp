@@ -329,6 +329,7 @@ int vg_destroy(vg_ctx* ctx) {
   if (ctx->dbg_cap_buf) (void)hipFree(ctx->dbg_cap_buf);
   markers_free(ctx);
   score_free(ctx);
+  ray_free(ctx);
   shard_free(ctx);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);

@@ -87,6 +87,59 @@ POINT_MATCH_DTYPE = np.dtype([("leaf", "<i4"), ("flag", "<i4"), ("r", "<f8"), ("
 SCORE_MAX_POSES = 65536
 
 
+class RayParams(ctypes.Structure):
+    """vg_ray_params."""
+    _fields_ = [("t_min", ctypes.c_double), ("t_max", ctypes.c_double), ("min_cos", ctypes.c_double),
+                ("max_steps", ctypes.c_int), ("pad", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class RayHit(ctypes.Structure):
+    """vg_ray_hit: one ray's record, 64 bytes."""
+    _fields_ = [("range", ctypes.c_double), ("var", ctypes.c_double), ("normal", ctypes.c_double * 3),
+                ("ndotd", ctypes.c_double), ("leaf", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_double)]
+
+
+class DiffParams(ctypes.Structure):
+    """vg_diff_params."""
+    _fields_ = [("ray", RayParams), ("gate_sigma", ctypes.c_double), ("gate_floor", ctypes.c_double),
+                ("reserved", ctypes.c_double * 4)]
+
+
+class DiffPoint(ctypes.Structure):
+    """vg_diff_point: vg_scan_diff's per-point record, 32 bytes."""
+    _fields_ = [("cls", ctypes.c_int32), ("leaf", ctypes.c_int32), ("r_meas", ctypes.c_double),
+                ("r_map", ctypes.c_double), ("gate", ctypes.c_double)]
+
+
+class DiffSummary(ctypes.Structure):
+    """vg_diff_summary."""
+    _fields_ = [("n", ctypes.c_int32 * 4), ("n_truncated", ctypes.c_int32), ("n_occupied_unknown", ctypes.c_int32),
+                ("sum_abs_consistent", ctypes.c_double), ("reserved", ctypes.c_double * 3)]
+
+
+RAY_HIT_DTYPE = np.dtype([("range", "<f8"), ("var", "<f8"), ("normal", "<f8", 3), ("ndotd", "<f8"), ("leaf", "<i4"),
+                          ("flags", "<i4"), ("reserved", "<f8")])
+DIFF_POINT_DTYPE = np.dtype([("cls", "<i4"), ("leaf", "<i4"), ("r_meas", "<f8"), ("r_map", "<f8"), ("gate", "<f8")])
+RAY_HIT, RAY_TRUNCATED, RAY_OCCUPIED, RAY_LEFT_RANGE, RAY_INVALID = 1, 2, 4, 8, 16
+DIFF_UNKNOWN, DIFF_CONSISTENT, DIFF_APPEARED, DIFF_VANISHED = 0, 1, 2, 3
+
+
+def ray_params(t_min=0.0, t_max=0.0, min_cos=0.0, max_steps=0):
+    """vg_ray_params; zeros take the defaults (100 m, 0.05, 4096)."""
+    p = RayParams()
+    p.t_min, p.t_max, p.min_cos, p.max_steps = t_min, t_max, min_cos, max_steps
+    return p
+
+
+def diff_params(gate_sigma=0.0, gate_floor=0.0, **ray):
+    """vg_diff_params; zeros take the defaults (3 sigma, no floor)."""
+    p = DiffParams()
+    p.ray = ray_params(**ray)
+    p.gate_sigma, p.gate_floor = gate_sigma, gate_floor
+    return p
+
+
 def reloc_params(half_xy=0.0, step_xy=0.0, half_z=0.0, step_z=0.0, half_yaw=0.0, step_yaw=0.0, refine_top=8,
                  refine_iters=8, min_match_ratio=0.5):
     p = RelocParams()
@@ -223,6 +276,12 @@ def lib():
             L.vg_fleet_sync.argtypes = [P]
             L.vg_fleet_destroy.argtypes = [P]
             L.vg_fleet_destroy.restype = None
+        L.has_raycast = hasattr(L, "vg_raycast")  # a build older than the ray-casting calls (A/B runs)
+        if L.has_raycast:
+            L.vg_raycast.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(RayParams), P]
+            L.vg_scan_diff.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(DiffParams), P,
+                                       ctypes.POINTER(DiffSummary)]
+            L.vgx_ray_ms.argtypes = [P, dp]
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -519,6 +578,39 @@ class Context:
                   "vg_relocalize")
         rec = {"matches": sc.matches, "in_map": sc.in_map, "cost": sc.cost, "sum_abs": sc.sum_abs, "nn": list(sc.nn)}
         return pose, rec, bool(ok.value)
+
+    def raycast(self, origins, dirs, **params):
+        """vg_raycast: rays from origins ((3,) shared by all, or (n, 3)) along dirs (n, 3), world frame, to
+        the first plane of the map; params: ray_params. Returns the n records (RAY_HIT_DTYPE)."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        p = ray_params(**params)
+        out = np.zeros(max(d.shape[0], 1), dtype=RAY_HIT_DTYPE)
+        self._chk(lib().vg_raycast(self.h, _d(o) if o.shape[0] else None, o.shape[0], _d(d) if d.shape[0] else None,
+                                   d.shape[0], ctypes.byref(p), out.ctypes.data), "vg_raycast")
+        return out[: d.shape[0]]
+
+    def scan_diff(self, xyz, pose=None, per_point=False, **params):
+        """vg_scan_diff: the scan xyz (n, 3; LiDAR frame) against the map's expected ranges at pose (12,)
+        [R row-major, p] (None: the context's state); params: diff_params. Returns the summary as a dict
+        (n: the four class counts by DIFF_*); with per_point also the n DIFF_POINT_DTYPE records."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        p = diff_params(**params)
+        pp = np.zeros(max(xyz.shape[0], 1), dtype=DIFF_POINT_DTYPE) if per_point else None
+        s = DiffSummary()
+        self._chk(lib().vg_scan_diff(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                     None if g is None else _d(g), ctypes.byref(p),
+                                     None if pp is None else pp.ctypes.data, ctypes.byref(s)), "vg_scan_diff")
+        rec = {"n": list(s.n), "n_truncated": s.n_truncated, "n_occupied_unknown": s.n_occupied_unknown,
+               "sum_abs_consistent": s.sum_abs_consistent}
+        return (rec, pp[: xyz.shape[0]]) if per_point else rec
+
+    def ray_ms(self):
+        """Device time of the last raycast slab's / scan_diff call's kernels (HIP events on the context stream), ms."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_ray_ms(self.h, ctypes.byref(ms)), "vgx_ray_ms")
+        return ms.value
 
     def _need_checkpoint(self):
         if not lib().has_checkpoint:
