@@ -477,6 +477,108 @@ typedef struct vg_diff_summary {
 int vg_scan_diff(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* prm,
                  vg_diff_point* per_point, vg_diff_summary* out);
 
+/* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
+ * One scan's classes do not say what changed: leaf planes reach to their cube's
+ * faces past a real edge, so a static scene already shows some VANISHED. The
+ * evidence that separates the two is per map leaf and per place, summed over many
+ * scans and sensors. The layer is a side structure next to a frozen map, owned by
+ * the context that owns the map; the map's bits never change.
+ *   per node (int32): n_consistent, n_vanished, n_occluded, n_scans, last_epoch;
+ *   a cell table for new surfaces: an open-addressed hash of 2^cell_hash_log2
+ *     slots keyed by the packed integer cell of a world point w, k_j = floor(w_j /
+ *     cell), |k_j| < 2^20, packed as root keys are; per slot int32 n_appeared,
+ *     n_scans, last_epoch and int64 sum_q[3];
+ *   totals (int64).
+ * Per point of an accumulated scan, classified exactly as vg_scan_diff does, with
+ * leaf the hit's node id: CONSISTENT n_consistent[leaf]++; VANISHED
+ * n_vanished[leaf]++; APPEARED n_occluded[leaf]++ and the point is charged to the
+ * cell of its world position w: n_appeared++, sum_q[j] += q_j, q_j =
+ * clamp((int)floor((w_j - k_j cell) / cell * 65536), 0, 65535); UNKNOWN: the
+ * totals only. Every accumulate call takes the next epoch (from 1); a leaf charged
+ * CONSISTENT or VANISHED, and a cell charged a point, counts the call once in its
+ * n_scans. Every sum is an integer sum, so the layer after a set of scans has the
+ * same bits in whatever order, from whichever context and at whatever position in
+ * the cloud the points arrived — as long as no point was dropped: a point whose
+ * cell finds the table full (the probe is bounded by the table size) is dropped
+ * and counted, and which points those are depends on the order. */
+typedef struct vg_change_params {
+  vg_diff_params diff;     /* zero fields: vg_scan_diff's defaults */
+  double cell;             /* cell edge in metres; <= 0: voxel_size / 4 */
+  int    cell_hash_log2;   /* <= 0: 20; at most 26 */
+  int    pad;
+  double reserved[4];
+} vg_change_params;
+typedef struct vg_change_query {
+  int    min_obs;          /* <= 0: 5 */
+  int    min_scans;        /* <= 0: 2 */
+  double vanished_ratio;   /* <= 0: 0.8 */
+  int    flags;            /* bit 0: every touched leaf / used cell, whether or not it meets its rule */
+  int    pad;
+  double reserved[4];
+} vg_change_query;
+typedef struct vg_change_leaf {   /* 112 bytes, no implicit padding */
+  int32_t node, layer, n_consistent, n_vanished, n_occluded, n_scans;
+  int32_t flags;                  /* bit 0: meets the removed rule */
+  int32_t pad;
+  double  voxel_center[3], quater_length, center[3], normal[3];  /* as vg_map_planes gives them */
+} vg_change_leaf;
+typedef struct vg_change_cell {   /* 56 bytes, no implicit padding */
+  int32_t key[3];                 /* k_j */
+  int32_t n_appeared, n_scans;
+  int32_t flags;                  /* bit 0: meets the added rule */
+  int32_t pad[2];
+  double  centroid[3];            /* cell (k_j + (sum_q_j + 0.5 n_appeared) / (65536 n_appeared)) */
+} vg_change_cell;
+typedef struct vg_change_totals { /* 128 bytes */
+  int64_t calls, points;          /* accumulate calls; their points */
+  int64_t n[4];                   /* points per class, indexed by VG_DIFF_* */
+  int64_t cells_used;             /* occupied slots of the cell table */
+  int64_t dropped;                /* APPEARED points whose cell found the table full */
+  int64_t out_of_range;           /* APPEARED points whose cell index left the key range */
+  int64_t leaves_touched;         /* nodes with a non-zero counter */
+  int64_t reserved[6];
+} vg_change_totals;
+/* vg_change_begin creates the layer (prm NULL: the defaults) on the context that
+ * owns a frozen map. VG_E_STATE: mapping is on, the context is sharded, inside a
+ * scan, itself attached, or has a layer already. VG_E_ARG: cell_hash_log2 > 26.
+ * vg_change_accumulate* may be called on the owner and on any tracker attached to
+ * it (a fleet's tracker between fleet steps included) and charges the owner's
+ * layer; VG_E_STATE when the map it reads has no layer. Arguments as
+ * vg_scan_diff's (pose12 NULL: the calling context's current state; out may be
+ * NULL here), and per_point and *out have vg_scan_diff's bits for the same input.
+ * The _dev form takes the cloud as three device arrays. Completes the calling
+ * context's outstanding work first; synchronous; calls into one layer are
+ * serialised inside the library, so they may come from several threads. n == 0 is
+ * legal: it takes an epoch and counts a call. A call that fails takes no epoch
+ * and leaves the totals as they were; after VG_E_HIP the layer's contents are
+ * undefined (vg_change_clear). A call that another thread's vg_change_end
+ * overtakes returns VG_E_STATE: the layer is looked up under the owner's lock.
+ * vg_change_report (owner or attached tracker): the leaves that meet the removed
+ * rule — n_vanished >= min_obs, n_scans >= min_scans and n_vanished >=
+ * vanished_ratio (n_vanished + n_consistent) — in ascending node id, and the cells
+ * that meet the added rule — n_appeared >= min_obs and n_scans >= min_scans — in
+ * ascending packed key; with flags bit 0 every touched leaf and used cell, the
+ * record's flags telling which meet the rule. min(count, cap) records are copied,
+ * the counts always returned; NULL arrays query the counts. q NULL: the defaults.
+ * totals may be NULL.
+ * vg_change_clear zeroes the layer (the epochs restart at 1); vg_change_end frees
+ * it. Both on the owner (VG_E_STATE without a layer).
+ * While a layer exists node ids must not move and the map must not change: on the
+ * owner vg_set_mapping(owner, 1), vg_reset, vg_checkpoint_load, vg_checkpoint_save
+ * (it compacts), vg_release_far with the compaction flag, vg_shard_* and
+ * vg_destroy return VG_E_STATE and change nothing. Frozen vg_step*, scoring,
+ * relocalise, ray-casting, vg_scan_diff, attach, detach and fleets work as before.
+ * The layer is not part of a checkpoint. */
+int vg_change_begin(vg_ctx* ctx, const vg_change_params* prm);
+int vg_change_accumulate(vg_ctx* ctx, const float* xyz, int n, const double* pose12,
+                         vg_diff_point* per_point, vg_diff_summary* out);
+int vg_change_accumulate_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int n,
+                             const double* pose12, vg_diff_summary* out);
+int vg_change_report(vg_ctx* ctx, const vg_change_query* q, vg_change_leaf* leaves, int leaf_cap, int* n_leaves,
+                     vg_change_cell* cells, int cell_cap, int* n_cells, vg_change_totals* totals);
+int vg_change_clear(vg_ctx* ctx);
+int vg_change_end(vg_ctx* ctx);
+
 /* ---- Map views: many sensors in one frozen map ------------------------------
  * vg_map_attach makes `tracker` a read-only view of `owner`'s map: every kernel
  * of the tracker that reads the map (the IEKF, vg_score_poses, vg_relocalize,

@@ -140,6 +140,39 @@ class LioCore {
     check(vg_scan_diff(ctx_, xyz, n, pose12, prm, per_point, &out), "vg_scan_diff");
     return out;
   }
+  // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
+  // owner or any tracker attached to it; prm / q null: the defaults
+  void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }
+  vg_diff_summary change_accumulate(const float* xyz, int n, const double* pose12 = nullptr,
+                                    vg_diff_point* per_point = nullptr) {
+    vg_diff_summary out;
+    check(vg_change_accumulate(ctx_, xyz, n, pose12, per_point, &out), "vg_change_accumulate");
+    return out;
+  }
+  vg_diff_summary change_accumulate_dev(const float* d_x, const float* d_y, const float* d_z, int n,
+                                        const double* pose12 = nullptr) {
+    vg_diff_summary out;
+    check(vg_change_accumulate_dev(ctx_, d_x, d_y, d_z, n, pose12, &out), "vg_change_accumulate_dev");
+    return out;
+  }
+  struct ChangeReport {
+    std::vector<vg_change_leaf> leaves;  // ascending node id
+    std::vector<vg_change_cell> cells;   // ascending packed key
+    vg_change_totals totals;
+  };
+  ChangeReport change_report(const vg_change_query* q = nullptr) {
+    ChangeReport r;
+    int nl = 0, nc = 0;
+    check(vg_change_report(ctx_, q, nullptr, 0, &nl, nullptr, 0, &nc, nullptr), "vg_change_report");
+    r.leaves.resize((size_t)nl);
+    r.cells.resize((size_t)nc);
+    check(vg_change_report(ctx_, q, r.leaves.data(), nl, &nl, r.cells.data(), nc, &nc, &r.totals), "vg_change_report");
+    r.leaves.resize((size_t)nl < r.leaves.size() ? (size_t)nl : r.leaves.size());
+    r.cells.resize((size_t)nc < r.cells.size() ? (size_t)nc : r.cells.size());
+    return r;
+  }
+  void change_clear() { check(vg_change_clear(ctx_), "vg_change_clear"); }
+  void change_end() { check(vg_change_end(ctx_), "vg_change_end"); }
   // map views (vina_gpu.h "Map views"): this context reads owner's frozen map. The owner
   // must outlive its views: destroy (or detach) the trackers first
   void attach(LioCore& owner) { check(vg_map_attach(ctx_, owner.ctx_), "vg_map_attach"); }

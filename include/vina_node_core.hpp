@@ -25,6 +25,7 @@
 #pragma once
 #include <cmath>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <unordered_set>
@@ -160,6 +161,7 @@ class NodeCore {
       scans_.erase(it);
       stepped++;
       if (visualization_) take_markers();
+      if (after_step_) after_step_();
       if (package_limit_ >= 0 && packages_ >= package_limit_) break;  // (the caller saves here, then spins on)
     }
     poll();
@@ -219,6 +221,10 @@ class NodeCore {
   }
   bool relocalized() const { return reloc_done_; }
   bool relocalize_ok() const { return reloc_ok_; }
+  // called after every stepped scan, before the next is taken: the caller reads what belongs to
+  // that scan alone (vg_scan_points and the state for vg_scan_diff / vg_change_accumulate, which
+  // complete the scan first)
+  void set_after_step(std::function<void()> fn) { after_step_ = std::move(fn); }
   void skip_packages(int n) { skip_ = n; }
   void set_package_limit(int n) { package_limit_ = n; }  // spin() returns once this many packages were taken (-1: no limit)
   int packages() const { return packages_; }             // packages sync_packages has delivered, skipped ones included
@@ -378,6 +384,7 @@ class NodeCore {
   vg_reloc_params reloc_prm_ = {};
   int publish_ = 0;  // vg_set_publish flags
   bool visualization_ = false;
+  std::function<void()> after_step_;
   std::vector<vg_plane_marker> markers_, marker_buf_;
   std::vector<int> marker_counts_;
 };

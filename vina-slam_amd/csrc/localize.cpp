@@ -19,6 +19,7 @@ int host_set_mapping(vg_ctx* ctx, int on) {
   if (on) {  // a map other contexts read, or another context's map, stays read-only
     VG_TRY(refuse_attached(ctx, "vg_set_mapping"));
     VG_TRY(refuse_owner(ctx, "vg_set_mapping"));
+    VG_TRY(refuse_layer(ctx, "vg_set_mapping"));
   }
   VG_TRY(host_ckpt_allowed(ctx, "vg_set_mapping", true));  // open scan, cold start initialising, sharded world > 1
   VG_TRY(host_sync(ctx));

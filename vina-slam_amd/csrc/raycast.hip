@@ -15,15 +15,9 @@
 // vg_scan_diff's class counts are integer atomics, one per wave and class; the
 // sum of |range - r| over the consistent points is stored per point and added
 // by one workgroup in a fixed order (k_diff_sum), as k_score_sum does.
-#include "vg_ray.h"
+#include "vg_diff.h"
 
 namespace vg {
-
-constexpr int kRayBlock = 256;
-
-struct Pose12 {
-  double v[12];
-};
 
 __global__ void __launch_bounds__(kRayBlock) k_raycast(double vs, DevMap m, const double* __restrict__ org,
                                                        int shared_origin, const double* __restrict__ dir, int n,
@@ -37,64 +31,25 @@ __global__ void __launch_bounds__(kRayBlock) k_raycast(double vs, DevMap m, cons
   out[i] = r;
 }
 
-// sum: the summary's six counts (zeroed by the caller); absv: per point |range - r| where consistent, else 0
+// sum: the summary's six counts (zeroed by the caller); absv: per point |range - r| where consistent, else 0.
+// The per-point body is vg_diff.h's, shared with k_change_accum (change.hip)
 __global__ void __launch_bounds__(kRayBlock) k_scan_diff(MP mp, DevMap m, const float* __restrict__ xyz, int n,
-                                                         Pose12 pose, RayPrm prm, double gate_sigma, double gate_floor,
-                                                         vg_diff_point* __restrict__ pp, double* __restrict__ absv,
-                                                         int* __restrict__ sum) {
+                                                         Pose12 pose, DiffPrm prm, vg_diff_point* __restrict__ pp,
+                                                         double* __restrict__ absv, int* __restrict__ sum) {
   const int i = blockIdx.x * kRayBlock + threadIdx.x;
   const bool valid = i < n;
   int cls = -1, rflags = 0;
   if (valid) {
-    const M3 R = ld_m3(pose.v);
-    const V3 p = ld_v3(pose.v + 9);
-    const V3 o = rigid(R, ld_v3(mp.extt), p);
     const V3 pb = v3(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]);
-    const V3 w = rigid(R, rigid(ld_m3(mp.extR), pb, ld_v3(mp.extt)), p);
-    const V3 dv = sub(w, o);
-    const double r = norm3(dv);
-    const double dept2 = (double)mp.dept * (double)mp.dept, beam2 = r * r * mp.beam_dv;
-    const double mc2 = prm.min_cos * prm.min_cos;
-    RayPrm q = prm;
-    const double reach = r + (gate_sigma * sqrt(dept2 + beam2 * (1.0 - mc2) / mc2) + 1.0);
-    if (reach < q.t_max) q.t_max = reach;
-    vg_ray_hit h;
-    ray_trace(m, mp.vs, o, dv, q, h);
-    rflags = h.flags;
     vg_diff_point dp;
-    dp.cls = VG_DIFF_UNKNOWN;
-    dp.leaf = -1;
-    dp.r_meas = r;
-    dp.r_map = 0.0;
-    dp.gate = 0.0;
-    double av = 0.0;
-    if (h.flags & kRayHit) {
-      const double c2 = h.ndotd * h.ndotd;
-      double g2 = gate_sigma * gate_sigma * (h.var + dept2 + beam2 * (1.0 - c2) / c2);
-      const double f2 = gate_floor * gate_floor;
-      if (!(g2 >= f2)) g2 = f2;
-      const double gate = sqrt(g2), diff = h.range - r;
-      dp.leaf = h.leaf;
-      dp.r_map = h.range;
-      dp.gate = gate;
-      if (fabs(diff) <= gate) {
-        dp.cls = VG_DIFF_CONSISTENT;
-        av = fabs(diff);
-      } else {
-        dp.cls = diff > gate ? VG_DIFF_APPEARED : VG_DIFF_VANISHED;
-      }
-    }
+    double av;
+    V3 w;
+    diff_point(mp, m, pb, pose, prm, dp, av, rflags, w);
     cls = dp.cls;
     if (pp) pp[i] = dp;
     absv[i] = av;
   }
-  // the wave's counts: one atomic per class that occurs
-  const int lane = threadIdx.x & 63;
-  for (int c = 0; c < 6; c++) {
-    const bool mine = c < 4 ? cls == c : (valid && (rflags & (c == 4 ? kRayTruncated : kRayOccupied)) != 0);
-    const unsigned long long b = __ballot(mine);
-    if (lane == 0 && b) atomicAdd(&sum[c], __popcll(b));
-  }
+  diff_wave_counts(cls, valid, rflags, sum);
 }
 
 // one workgroup: thread t adds the points t, t + 256, ... in that order, then a fixed tree over the threads
@@ -118,17 +73,11 @@ __global__ void __launch_bounds__(kRayBlock) k_diff_sum(const double* __restrict
 
 // ---- host side
 
-static RayPrm ray_prm(const vg_ray_params* p) {
-  RayPrm q;
-  q.t_min = p ? p->t_min : 0.0;
-  q.t_max = p && p->t_max > 0.0 ? p->t_max : 100.0;
-  q.min_cos = p && p->min_cos > 0.0 ? p->min_cos : 0.05;
-  q.max_steps = p && p->max_steps > 0 ? p->max_steps : 4096;
-  q.pad = 0;
-  return q;
+void diff_sum_launch(hipStream_t s, const double* absv, int n, vg_diff_summary* d_sum) {
+  k_diff_sum<<<1, kRayBlock, 0, s>>>(absv, n, d_sum);
 }
 
-static int ray_bufs(vg_ctx* ctx) {
+int ray_bufs(vg_ctx* ctx) {
   RayBufs& b = ctx->ray;
   if (b.cap > 0) return VG_OK;
   const size_t cap = (size_t)(ctx->cap.max_points_per_scan > 0 ? ctx->cap.max_points_per_scan : 1);
@@ -174,9 +123,7 @@ int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
   VG_TRY(ray_bufs(ctx));
   RayBufs& b = ctx->ray;
   hipStream_t s = ctx->stream;
-  const RayPrm q = ray_prm(prm ? &prm->ray : nullptr);
-  const double gs = prm && prm->gate_sigma > 0.0 ? prm->gate_sigma : 3.0;
-  const double gf = prm && prm->gate_floor > 0.0 ? prm->gate_floor : 0.0;
+  const DiffPrm q = diff_prm(prm);
   Pose12 pose;
   for (int e = 0; e < 12; e++) pose.v[e] = pose12[e];
   float* d_xyz = reinterpret_cast<float*>(b.dir);
@@ -185,9 +132,9 @@ int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
   VG_HIP(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_diff_summary), s));
   VG_HIP(hipEventRecord(b.ev[0], s));
-  k_scan_diff<<<(n + kRayBlock - 1) / kRayBlock, kRayBlock, 0, s>>>(mp, ctx->map, d_xyz, n, pose, q, gs, gf, d_pp, b.org,
+  k_scan_diff<<<(n + kRayBlock - 1) / kRayBlock, kRayBlock, 0, s>>>(mp, ctx->map, d_xyz, n, pose, q, d_pp, b.org,
                                                                    reinterpret_cast<int*>(d_sum));
-  k_diff_sum<<<1, kRayBlock, 0, s>>>(b.org, n, d_sum);
+  diff_sum_launch(s, b.org, n, d_sum);
   VG_HIP(hipEventRecord(b.ev[1], s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_diff_summary), hipMemcpyDeviceToHost, s));

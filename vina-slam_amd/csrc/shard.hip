@@ -184,6 +184,7 @@ static int shard_common(vg_ctx* ctx, int rank, int world) {
   }
   VG_TRY(refuse_attached(ctx, "vg_shard"));  // a map view (vg_map_attach) is unsharded on both sides
   VG_TRY(refuse_owner(ctx, "vg_shard"));
+  VG_TRY(refuse_layer(ctx, "vg_shard"));
   if (host_win_count(ctx) != 0 || ctx->shard.mode != 0) {
     ctx->err = "vg_shard: call once, before the first scan";
     return VG_E_STATE;

@@ -407,6 +407,35 @@ struct RayBufs {
   int cap = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the last call's kernels (vgx_ray_ms)
 };
+// The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
+// side structure of the context that owns a frozen map, never part of DevMap.
+// Only integer atomics write it, one accumulate call at a time (vg_ctx::change_mu of the owner).
+struct ChangeNode {  // 20 B per node of the owner's pool
+  int n_consistent, n_vanished, n_occluded, n_scans, last_epoch;
+};
+struct ChangeCell {  // 40 B per slot of the cell table (the slot's key: ChangeDev::ckey)
+  long long sum_q[3];
+  int n_appeared, n_scans, last_epoch, pad;
+};
+enum { kChgDropped = 0, kChgOutOfRange = 1, kChgTot = 2 };
+struct ChangeDev {   // what the kernels take
+  ChangeNode* node = nullptr;          // cap_nodes
+  unsigned long long* ckey = nullptr;  // mask + 1 packed cell keys, kKeyEmpty: free
+  ChangeCell* cell = nullptr;          // mask + 1
+  long long* tot = nullptr;            // kChgTot device totals
+  int cap_nodes = 0, mask = 0;
+  double cell_size = 0.0;
+};
+struct ChangeLayer {
+  ChangeDev d;
+  vg_diff_params diff;   // as vg_change_begin was given them
+  int epoch = 0;         // accumulate calls that succeeded so far
+  long long calls = 0, points = 0, cls[4] = {0, 0, 0, 0};
+  int* d_blk = nullptr;  // the report's per-workgroup counts / offsets (blk_n entries)
+  int blk_n = 0;
+  void* d_out = nullptr; // the report's record staging, grown on demand
+  size_t out_bytes = 0;
+};
 // window view for the map kernels, built on the device from DState::xs
 struct WinArg {
   int mp[kMaxWin];      // mp[] ring (octree.cpp:75)
@@ -535,6 +564,9 @@ struct vg_ctx {
   void* fleet = nullptr;      // a fleet's tracker (vg_fleet_create): stepped only through the fleet
   vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
   vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
+  vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
+  std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
+                             // (the owner or an attached tracker) reads `change` only while holding it
   vg_stats stats;
   void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
   // stage timing with HIP events on the context stream (vg_profile)
@@ -921,6 +953,20 @@ int raycast_dev(vg_ctx* ctx, const MP& mp, const double* origins, int n_origins,
 int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
                   const vg_diff_params* prm, vg_diff_point* per_point, vg_diff_summary* out);
 void ray_free(vg_ctx* ctx);
+int ray_bufs(vg_ctx* ctx);  // the staging, allocated on first use
+void diff_sum_launch(hipStream_t s, const double* absv, int n, vg_diff_summary* d_sum);  // k_diff_sum
+// change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
+int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
+void change_free(ChangeLayer* L);
+int change_clear_dev(vg_ctx* ctx, ChangeLayer* L);
+// one scan into L at `epoch`, through ctx's map, staging and stream; x, y, z: host AoS (stride 3, dev false) or
+// device arrays (stride 1)
+int change_accum_dev(vg_ctx* ctx, ChangeLayer* L, const MP& mp, const float* x, const float* y, const float* z,
+                     int stride, bool dev, int n, const double* pose12, int epoch, vg_diff_point* per_point,
+                     vg_diff_summary* out);
+// every selected record, in report order; tot4: points dropped, out of range, nodes touched, cells used
+int change_report_dev(vg_ctx* ctx, ChangeLayer* L, const vg_change_query& q, std::vector<vg_change_leaf>& leaves,
+                      std::vector<vg_change_cell>& cells, long long* tot4);
 // raycast_host.cpp: the two calls behind the C-ABI
 int host_raycast(vg_ctx* ctx, const double* origins, int n_origins, const double* dirs, int n,
                  const vg_ray_params* prm, vg_ray_hit* out);
@@ -940,6 +986,12 @@ inline int refuse_owner(vg_ctx* ctx, const char* who) {
   if (ctx->views == 0) return VG_OK;
   ctx->err = std::string(who) + ": " + std::to_string(ctx->views) +
              " context(s) are attached to this context's map (vg_map_detach them first)";
+  return VG_E_STATE;
+}
+// what a change layer rules out on its owner (vina_gpu.h "Change layer"): node ids must not move, the map not change
+inline int refuse_layer(vg_ctx* ctx, const char* who) {
+  if (!ctx->change) return VG_OK;
+  ctx->err = std::string(who) + ": the context's map has a change layer (vg_change_end first)";
   return VG_E_STATE;
 }
 inline int refuse_fleet(vg_ctx* ctx, const char* who) {

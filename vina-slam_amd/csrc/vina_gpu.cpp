@@ -310,6 +310,7 @@ int vg_destroy(vg_ctx* ctx) {
   if (!ctx) return VG_OK;
   // a map other contexts read, or a fleet's tracker, stays; a tracker lets go of the owner's map first
   VG_TRY(refuse_owner(ctx, "vg_destroy"));
+  VG_TRY(refuse_layer(ctx, "vg_destroy"));
   VG_TRY(refuse_fleet(ctx, "vg_destroy"));
   if (ctx->view_of) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -378,6 +379,7 @@ int vg_reset(vg_ctx* ctx) {
   if (!ctx) return VG_E_ARG;
   VG_TRY(refuse_attached(ctx, "vg_reset"));
   VG_TRY(refuse_owner(ctx, "vg_reset"));
+  VG_TRY(refuse_layer(ctx, "vg_reset"));
   VG_HIP(hipStreamSynchronize(ctx->stream_ds));
   VG_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->stream_iekf) VG_HIP(hipStreamSynchronize(ctx->stream_iekf));
@@ -650,6 +652,7 @@ int vg_scan_points(vg_ctx* ctx, float* xyz, int cap, int* n) {
 int vg_release_far(vg_ctx* ctx, int flags, long long* out) {
   if (!ctx || !out || (flags & ~3)) return VG_E_ARG;
   if (flags & 1) VG_TRY(refuse_owner(ctx, "vg_release_far (compaction)"));  // node ids would move under the views
+  if (flags & 1) VG_TRY(refuse_layer(ctx, "vg_release_far (compaction)"));  // ... and under the change layer
   if (!(flags & 3)) {  // nothing asked but the release: no wait unless one is pending
     VG_TRY(host_poll(ctx));
     if (!host_release_pending(ctx)) {
@@ -665,6 +668,7 @@ int vg_checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes) {
   if (!ctx || !path) return VG_E_ARG;
   VG_TRY(refuse_attached(ctx, "vg_checkpoint_save"));
   VG_TRY(refuse_owner(ctx, "vg_checkpoint_save"));  // (the save compacts: node ids would move under the views)
+  VG_TRY(refuse_layer(ctx, "vg_checkpoint_save"));
   return checkpoint_save(ctx, path, bytes, nullptr);
 }
 
@@ -672,6 +676,7 @@ int vg_checkpoint_load(vg_ctx* ctx, const char* path) {
   if (!ctx || !path) return VG_E_ARG;
   VG_TRY(refuse_attached(ctx, "vg_checkpoint_load"));
   VG_TRY(refuse_owner(ctx, "vg_checkpoint_load"));
+  VG_TRY(refuse_layer(ctx, "vg_checkpoint_load"));
   return checkpoint_load(ctx, path, nullptr);
 }
 

@@ -14,13 +14,25 @@
 //
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
-//        [--map FILE --localize [--guess "x y z yaw"]]
+//        [--map FILE --localize [--guess "x y z yaw"] [--scan-diff] [--changes FILE [--changes-scans FILE]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
 // --map FILE --localize: load the map FILE (a checkpoint), relocalise on the first scan around the
 // guess (default: the map's saved pose; --guess: position and yaw about z, the saved roll / pitch kept;
 // window +-2 m / 0.25 m, +-30 deg / 2.5 deg) and run with the map frozen; the TUM output is as always.
+// --scan-diff (with --localize): every localised scan's downsampled cloud is checked against the map at
+// its IEKF pose (vg_scan_diff) and one line per scan goes to stdout ahead of the summary line:
+//   scan_diff <scan index> <scan end time> <n_ds> <unknown> <consistent> <appeared> <vanished>
+// --changes FILE (with --localize): a change layer is begun on the loaded map, every localised scan's
+// downsampled cloud accumulated at its IEKF pose (vg_change_accumulate; its summary feeds --scan-diff),
+// and the report of everything touched (query flags 1, default rule) written as CSV at the end, doubles
+// with 17 significant digits, one record per line by kind:
+//   leaf,node,layer,n_consistent,n_vanished,n_occluded,n_scans,flags,vcx,vcy,vcz,quater_length,cx,cy,cz,nx,ny,nz
+//   cell,kx,ky,kz,n_appeared,n_scans,flags,x,y,z
+//   totals,calls,points,unknown,consistent,appeared,vanished,cells_used,dropped,out_of_range,leaves_touched
+// (flags bit 0: the leaf meets the removed rule / the cell the added rule). --changes-scans FILE: what was
+// accumulated, per scan int32 n, double pose[12], float xyz[3 n], to check the report against the API.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,9 +45,9 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
-  std::string ck_out, resume, map_file, guess_s;
+  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans;
   int ck_at = -1;
-  bool localize = false;
+  bool localize = false, scan_diff = false;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
     if (i + 1 < argc0 && a == "--checkpoint-out") ck_out = argv0[++i];
@@ -43,11 +55,23 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--resume") resume = argv0[++i];
     else if (i + 1 < argc0 && a == "--map") map_file = argv0[++i];
     else if (i + 1 < argc0 && a == "--guess") guess_s = argv0[++i];
+    else if (i + 1 < argc0 && a == "--changes") changes_file = argv0[++i];
+    else if (i + 1 < argc0 && a == "--changes-scans") changes_scans = argv0[++i];
     else if (a == "--localize") localize = true;
+    else if (a == "--scan-diff") scan_diff = true;
     else pos.push_back(argv0[i]);
   }
   const int argc = (int)pos.size();
   char** argv = pos.data();
+  const bool changes = !changes_file.empty();
+  if ((scan_diff || changes) && !localize) {
+    fprintf(stderr, "%s: --scan-diff and --changes need --map FILE --localize\n", argv0[0]);
+    return 2;
+  }
+  if (!changes_scans.empty() && !changes) {
+    fprintf(stderr, "%s: --changes-scans needs --changes FILE\n", argv0[0]);
+    return 2;
+  }
   if (argc < 3 || (ck_out.empty() != (ck_at < 0)) || (localize != !map_file.empty())) {
     fprintf(stderr, "usage: %s events.bin out_tum.txt [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]\n", argv[0]);
     return 2;
@@ -129,6 +153,41 @@ int main(int argc0, char** argv0) {
       prm.half_yaw = 30 * M_PI / 180, prm.step_yaw = 2.5 * M_PI / 180;
       node.relocalize(g, prm);
     }
+    // --scan-diff / --changes: after every localised scan, its downsampled cloud against the map at its IEKF pose
+    FILE* fscans = nullptr;
+    int n_diffed = 0;
+    std::vector<float> ds;
+    if (changes) {
+      node.lio().change_begin();
+      if (!changes_scans.empty() && !(fscans = fopen(changes_scans.c_str(), "wb"))) {
+        perror("changes-scans");
+        return 1;
+      }
+    }
+    if (scan_diff || changes)
+      node.set_after_step([&]() {
+        vg_ctx* c = node.lio().raw();
+        int n = 0;
+        double st[VG_STATE_LEN];
+        if (vg_scan_points(c, nullptr, 0, &n) != VG_OK || vg_get_state(c, st) != VG_OK)
+          throw vina_gpu::Error(VG_E_STATE, std::string("after the scan: ") + vg_last_error(c));
+        ds.resize((size_t)3 * (n > 0 ? n : 1));
+        if (n > 0 && vg_scan_points(c, ds.data(), n, &n) != VG_OK)
+          throw vina_gpu::Error(VG_E_STATE, std::string("vg_scan_points: ") + vg_last_error(c));
+        const double* pose = st + 1;  // R row-major, p: the pose after the scan's IEKF
+        const vg_diff_summary sm = changes ? node.lio().change_accumulate(ds.data(), n, pose)
+                                           : node.lio().scan_diff(ds.data(), n, pose);
+        if (fscans) {
+          const int32_t n32 = n;
+          if (fwrite(&n32, sizeof(n32), 1, fscans) != 1 || fwrite(pose, sizeof(double), 12, fscans) != 12 ||
+              fwrite(ds.data(), sizeof(float), (size_t)3 * n, fscans) != (size_t)3 * n)
+            throw vina_gpu::Error(VG_E_STATE, "writing the --changes-scans file failed");
+        }
+        if (scan_diff)
+          printf("scan_diff %d %.9f %d %d %d %d %d\n", n_diffed, st[0], n, sm.n[VG_DIFF_UNKNOWN], sm.n[VG_DIFF_CONSISTENT],
+                 sm.n[VG_DIFF_APPEARED], sm.n[VG_DIFF_VANISHED]);
+        n_diffed++;
+      });
     if (ck_at >= 0) node.set_package_limit(ck_at);
     std::vector<unsigned char> rec;
     int n_imu = 0, n_msg = 0, n_step = 0;
@@ -183,6 +242,38 @@ int main(int argc0, char** argv0) {
       }
     }
     if (fm) fclose(fm);
+    if (fscans && fclose(fscans) != 0) {
+      perror("changes-scans");
+      return 1;
+    }
+    if (changes) {  // everything the layer holds, the records' flags telling what meets the default rule
+      vg_change_query q;
+      memset(&q, 0, sizeof(q));
+      q.flags = 1;
+      const vina_gpu::LioCore::ChangeReport r = node.lio().change_report(&q);
+      node.lio().change_end();
+      FILE* fc = fopen(changes_file.c_str(), "w");
+      if (!fc) {
+        perror("changes");
+        return 1;
+      }
+      for (const vg_change_leaf& l : r.leaves)
+        fprintf(fc, "leaf,%d,%d,%d,%d,%d,%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", l.node, l.layer,
+                l.n_consistent, l.n_vanished, l.n_occluded, l.n_scans, l.flags, l.voxel_center[0], l.voxel_center[1],
+                l.voxel_center[2], l.quater_length, l.center[0], l.center[1], l.center[2], l.normal[0], l.normal[1],
+                l.normal[2]);
+      for (const vg_change_cell& c : r.cells)
+        fprintf(fc, "cell,%d,%d,%d,%d,%d,%d,%.17g,%.17g,%.17g\n", c.key[0], c.key[1], c.key[2], c.n_appeared, c.n_scans,
+                c.flags, c.centroid[0], c.centroid[1], c.centroid[2]);
+      const vg_change_totals& t = r.totals;
+      fprintf(fc, "totals,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld\n", (long long)t.calls, (long long)t.points,
+              (long long)t.n[0], (long long)t.n[1], (long long)t.n[2], (long long)t.n[3], (long long)t.cells_used,
+              (long long)t.dropped, (long long)t.out_of_range, (long long)t.leaves_touched);
+      if (fclose(fc) != 0) {
+        perror("changes");
+        return 1;
+      }
+    }
     const std::vector<float> w = node.scan_world();
     if (!node.write_tum(argv[2])) {
       perror("tum");

@@ -118,6 +118,33 @@ class DiffSummary(ctypes.Structure):
                 ("sum_abs_consistent", ctypes.c_double), ("reserved", ctypes.c_double * 3)]
 
 
+class ChangeParams(ctypes.Structure):
+    """vg_change_params."""
+    _fields_ = [("diff", DiffParams), ("cell", ctypes.c_double), ("cell_hash_log2", ctypes.c_int),
+                ("pad", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class ChangeQuery(ctypes.Structure):
+    """vg_change_query."""
+    _fields_ = [("min_obs", ctypes.c_int), ("min_scans", ctypes.c_int), ("vanished_ratio", ctypes.c_double),
+                ("flags", ctypes.c_int), ("pad", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class ChangeTotals(ctypes.Structure):
+    """vg_change_totals, 128 bytes."""
+    _fields_ = [("calls", ctypes.c_int64), ("points", ctypes.c_int64), ("n", ctypes.c_int64 * 4),
+                ("cells_used", ctypes.c_int64), ("dropped", ctypes.c_int64), ("out_of_range", ctypes.c_int64),
+                ("leaves_touched", ctypes.c_int64), ("reserved", ctypes.c_int64 * 6)]
+
+
+# vg_change_leaf (112 bytes) and vg_change_cell (56 bytes) as numpy record types
+CHANGE_LEAF_DTYPE = np.dtype([("node", "<i4"), ("layer", "<i4"), ("n_consistent", "<i4"), ("n_vanished", "<i4"),
+                              ("n_occluded", "<i4"), ("n_scans", "<i4"), ("flags", "<i4"), ("pad", "<i4"),
+                              ("voxel_center", "<f8", 3), ("quater_length", "<f8"), ("center", "<f8", 3),
+                              ("normal", "<f8", 3)])
+CHANGE_CELL_DTYPE = np.dtype([("key", "<i4", 3), ("n_appeared", "<i4"), ("n_scans", "<i4"), ("flags", "<i4"),
+                              ("pad", "<i4", 2), ("centroid", "<f8", 3)])
+
 RAY_HIT_DTYPE = np.dtype([("range", "<f8"), ("var", "<f8"), ("normal", "<f8", 3), ("ndotd", "<f8"), ("leaf", "<i4"),
                           ("flags", "<i4"), ("reserved", "<f8")])
 DIFF_POINT_DTYPE = np.dtype([("cls", "<i4"), ("leaf", "<i4"), ("r_meas", "<f8"), ("r_map", "<f8"), ("gate", "<f8")])
@@ -282,6 +309,15 @@ def lib():
             L.vg_scan_diff.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(DiffParams), P,
                                        ctypes.POINTER(DiffSummary)]
             L.vgx_ray_ms.argtypes = [P, dp]
+        L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
+        if L.has_change:
+            L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
+            L.vg_change_accumulate.argtypes = [P, fp, ctypes.c_int, dp, P, ctypes.POINTER(DiffSummary)]
+            L.vg_change_accumulate_dev.argtypes = [P, P, P, P, ctypes.c_int, dp, ctypes.POINTER(DiffSummary)]
+            L.vg_change_report.argtypes = [P, ctypes.POINTER(ChangeQuery), P, ctypes.c_int, ip, P, ctypes.c_int, ip,
+                                           ctypes.POINTER(ChangeTotals)]
+            L.vg_change_clear.argtypes = [P]
+            L.vg_change_end.argtypes = [P]
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -605,6 +641,69 @@ class Context:
         rec = {"n": list(s.n), "n_truncated": s.n_truncated, "n_occupied_unknown": s.n_occupied_unknown,
                "sum_abs_consistent": s.sum_abs_consistent}
         return (rec, pp[: xyz.shape[0]]) if per_point else rec
+
+    # ---- the change layer (vina_gpu.h "Change layer")
+    def change_begin(self, cell=0.0, cell_hash_log2=0, **diff):
+        """vg_change_begin on the context that owns a frozen map; diff: diff_params; zeros take the
+        defaults (cell = voxel_size / 4, 2^20 slots)."""
+        p = ChangeParams()
+        p.diff = diff_params(**diff)
+        p.cell, p.cell_hash_log2 = cell, cell_hash_log2
+        self._chk(lib().vg_change_begin(self.h, ctypes.byref(p)), "vg_change_begin")
+
+    @staticmethod
+    def _summary(s):
+        return {"n": list(s.n), "n_truncated": s.n_truncated, "n_occupied_unknown": s.n_occupied_unknown,
+                "sum_abs_consistent": s.sum_abs_consistent}
+
+    def change_accumulate(self, xyz, pose=None, per_point=False):
+        """vg_change_accumulate: scan_diff's arguments and returns, and the scan's evidence charged to the
+        layer of the map this context reads (its own, or its owner's when attached)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pp = np.zeros(max(xyz.shape[0], 1), dtype=DIFF_POINT_DTYPE) if per_point else None
+        s = DiffSummary()
+        self._chk(lib().vg_change_accumulate(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                             None if g is None else _d(g), None if pp is None else pp.ctypes.data,
+                                             ctypes.byref(s)), "vg_change_accumulate")
+        rec = self._summary(s)
+        return (rec, pp[: xyz.shape[0]]) if per_point else rec
+
+    def change_accumulate_dev(self, dx, dy, dz, n, pose=None):
+        """vg_change_accumulate_dev: the cloud as three device arrays (addresses) of n floats."""
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        s = DiffSummary()
+        self._chk(lib().vg_change_accumulate_dev(self.h, ctypes.c_void_p(dx), ctypes.c_void_p(dy), ctypes.c_void_p(dz),
+                                                 n, None if g is None else _d(g), ctypes.byref(s)),
+                  "vg_change_accumulate_dev")
+        return self._summary(s)
+
+    def change_report(self, min_obs=0, min_scans=0, vanished_ratio=0.0, flags=0):
+        """vg_change_report: (leaves (CHANGE_LEAF_DTYPE, ascending node id), cells (CHANGE_CELL_DTYPE,
+        ascending packed key), totals as a dict). Zeros take the defaults (5, 2, 0.8); flags bit 0: every
+        touched leaf and used cell, the records' flags telling which meet their rule."""
+        q = ChangeQuery()
+        q.min_obs, q.min_scans, q.vanished_ratio, q.flags = min_obs, min_scans, vanished_ratio, flags
+        nl, nc = ctypes.c_int(0), ctypes.c_int(0)
+        t = ChangeTotals()
+        self._chk(lib().vg_change_report(self.h, ctypes.byref(q), None, 0, ctypes.byref(nl), None, 0, ctypes.byref(nc),
+                                         None), "vg_change_report")
+        leaves = np.zeros(max(nl.value, 1), dtype=CHANGE_LEAF_DTYPE)
+        cells = np.zeros(max(nc.value, 1), dtype=CHANGE_CELL_DTYPE)
+        self._chk(lib().vg_change_report(self.h, ctypes.byref(q), leaves.ctypes.data, nl.value, ctypes.byref(nl),
+                                         cells.ctypes.data, nc.value, ctypes.byref(nc), ctypes.byref(t)),
+                  "vg_change_report")
+        tot = {k: (list(getattr(t, k)) if k == "n" else getattr(t, k)) for k, _ in ChangeTotals._fields_
+               if k != "reserved"}
+        return leaves[: nl.value], cells[: nc.value], tot
+
+    def change_clear(self):
+        """vg_change_clear: the layer zeroed, the epochs restart."""
+        self._chk(lib().vg_change_clear(self.h), "vg_change_clear")
+
+    def change_end(self):
+        """vg_change_end: the layer freed."""
+        self._chk(lib().vg_change_end(self.h), "vg_change_end")
 
     def ray_ms(self):
         """Device time of the last raycast slab's / scan_diff call's kernels (HIP events on the context stream), ms."""
