@@ -579,6 +579,110 @@ int vg_change_report(vg_ctx* ctx, const vg_change_query* q, vg_change_leaf* leav
 int vg_change_clear(vg_ctx* ctx);
 int vg_change_end(vg_ctx* ctx);
 
+/* ---- Place index: global relocalisation in a frozen map ------------------------
+ * vg_relocalize needs a rough guess. The place index supplies one from a single
+ * scan and the gravity direction: a side structure next to a frozen map (as the
+ * change layer: owned by the context that owns the map, never part of a
+ * checkpoint) that holds, per sample position ("place"), the polar range image
+ * the map shows from there; a scan is binned into the same image, compared with
+ * every place under every circular azimuth shift, and the best few (place, yaw)
+ * pairs go to vg_relocalize's grid, scoring and refinement.
+ *
+ * The descriptor: n_az azimuth x n_el elevation bins, one uint16 per bin, range
+ * in units of 1 / 512 m clipped to 65535, 0 = none; bin (e, a) is entry
+ * e * n_az + a. The frame is (ex, ey, up): up = -g / |g| of the building
+ * context's state, ex = world x made perpendicular to up (world y where |up.x|
+ * >= 0.9), ey = up x ex. Azimuth bin a covers [a, a + 1) 2 pi / n_az from ex
+ * towards ey, elevation bin e covers el_min + [e, e + 1) (el_max - el_min) /
+ * n_el; a bin's centre direction is cos(el) (cos(az) ex + sin(az) ey) + sin(el)
+ * up at the middle of both spans.
+ *   Map side: bin (e, a) of a place is rint(512 range) of the vg_raycast ray from
+ *   the place's position along the bin's centre direction over (ray.t_min,
+ *   t_max]; a miss is 0.
+ *   Scan side: a point x (LiDAR frame) is v = R_level ext_R x, R_level any
+ *   rotation with the sensor's roll and pitch (its yaw is the unknown); r = |v|,
+ *   q = rint(512 r), its bin from the azimuth atan2(v.ey, v.ex) and the elevation
+ *   asin(v.up / r); points outside the elevation span or with r > t_max (or r =
+ *   0) are dropped. A bin's value is (sum q + n / 2) / n over its n points in
+ *   integer arithmetic, so it does not depend on the points' order.
+ *   Match: score(place, s) = sum over the scan's non-empty bins (e, a) of
+ *   min(|place[e][(a + s) mod n_az] - scan[e][a]|, clip_q), clip_q = rint(512
+ *   clip), an empty place bin charged clip_q; int32. Shift s is the yaw 2 pi s /
+ *   n_az about up: the sensor's rotation is Rz_up(yaw) R_level. */
+typedef struct vg_places_params {
+  int    n_az, n_el;       /* <= 0: 120, 12. At most 256 and 32, and n_az * n_el <= 4096 */
+  double el_min, el_max;   /* radians, within [-pi/2, pi/2]; both 0: -+30 degrees */
+  double t_max;            /* metres; <= 0: 60. Replaces ray.t_max */
+  double clip;             /* metres; <= 0: 2 */
+  int    min_bins;         /* a place with fewer hit bins is invalid; <= 0: n_az * n_el / 8 */
+  int    pad;
+  vg_ray_params ray;       /* t_min, min_cos, max_steps as vg_raycast takes them */
+  double reserved[4];
+} vg_places_params;
+typedef struct vg_place_candidate {   /* 48 bytes, no implicit padding */
+  int32_t place, shift;               /* index into the build's positions; azimuth shift in bins */
+  int32_t score, n_valid;             /* the match's score; the scan's non-empty bins */
+  double  pos[3];                     /* the place's position (a LiDAR origin, world) */
+  double  yaw;                        /* 2 pi shift / n_az */
+} vg_place_candidate;
+/* The bin-centre directions in the descriptor's own frame (x = ex, y = ey, z =
+ * up; the world frame where gravity is along -z), without a device: out (may be
+ * NULL) cap x 3 doubles, entry e * n_az + a; *count = n_az * n_el. The index
+ * casts exactly these (as ex, ey, up combinations). prm NULL: the defaults. A
+ * limit exceeded, an empty or out-of-range elevation span, NULL count, cap < 0:
+ * VG_E_ARG. */
+int vg_places_dirs(const vg_places_params* prm, double* out, int cap, int* count);
+/* Build the index over M positions (M x 3 doubles, LiDAR origins in the world)
+ * on the context that owns a frozen map; an existing index is replaced. A
+ * place's row depends on the place and the map alone (the same bytes at any M
+ * and order). VG_E_STATE: mapping is on, the context is sharded, inside a scan,
+ * or itself attached. VG_E_ARG: NULL, M <= 0, M * n_az * n_el >= 2^30, a limit
+ * exceeded. Completes outstanding work; synchronous.
+ * While an index exists the owner refuses what would change the map, as with a
+ * change layer: vg_set_mapping(owner, 1), vg_reset, vg_checkpoint_load,
+ * vg_checkpoint_save, vg_release_far with the compaction flag and vg_shard_*
+ * return VG_E_STATE. vg_destroy ends the index. */
+int vg_places_build(vg_ctx* ctx, const double* positions, int M, const vg_places_params* prm);
+/* M, the number of valid places (hit_bins >= min_bins), and optionally the
+ * descriptors (M * n_el * n_az uint16) and the per-place hit-bin counts. Every
+ * pointer may be NULL. */
+int vg_places_info(vg_ctx* ctx, int* M, int* n_valid, uint16_t* desc, int32_t* hit_bins);
+/* The scan's descriptor alone: desc (n_el * n_az uint16) and n_per_bin (int32),
+ * either may be NULL. R_level9: row-major rotation, NULL = the calling context's
+ * current R. n == 0 gives an all-zero descriptor. */
+int vg_places_scan(vg_ctx* ctx, const float* xyz, int n, const double* R_level9, uint16_t* desc,
+                   int32_t* n_per_bin);
+/* Scan pass + match pass, then the top_k smallest records over every valid
+ * place's two entries — its best shift (equal scores: the lower s) and its best
+ * shift at least n_az / 4 bins (circularly) away from that one — ordered by
+ * ascending score, then place, then shift. *n_out <= top_k records are written;
+ * 0 when n == 0, the scan has no non-empty bin or no place is valid.
+ * scores_all (may be NULL): M x n_az int32, INT32_MAX for invalid places.
+ * The candidate's pose: R = Rz_up(yaw) R_level, p = pos - R ext_t. */
+int vg_places_query(vg_ctx* ctx, const float* xyz, int n, const double* R_level9, int top_k,
+                    vg_place_candidate* out, int* n_out, int32_t* scores_all);
+/* Frees the index (VG_E_STATE without one, or on an attached tracker). */
+int vg_places_end(vg_ctx* ctx);
+/* vg_places_query, then vg_relocalize's own grid, scoring and refinement around
+ * each candidate's pose (at most 4096 candidates); a record that verifies
+ * beats one that does not, among equals vg_relocalize's ranking decides, and
+ * the winner is refined again from where it stands (a grid of one hypothesis,
+ * at most 4 times) until it rests. prm NULL: half_xy = half the median nearest-neighbour spacing of the
+ * places in the ex-ey plane at step 0.25 m, half_yaw = 1.5 azimuth bins at a
+ * third of a bin, no z search, vg_relocalize's defaults for the rest. ok,
+ * install, out_pose and out_score as vg_relocalize's; out_place (may be NULL):
+ * the winning candidate. No candidate or a failed verification: VG_OK, *ok = 0,
+ * the context's state untouched.
+ * vg_places_info / _scan / _query and vg_relocalize_global may be called on the
+ * owner and on any tracker attached to it (the owner's index; calls into one
+ * index are serialised inside the library; a call that another thread's
+ * vg_places_end overtakes returns VG_E_STATE). VG_E_ARG: NULL ctx, xyz (n > 0),
+ * out / n_out / out_pose / ok, n < 0 or above max_points_per_scan, top_k <= 0.
+ * Unsharded contexts, between scans. */
+int vg_relocalize_global(vg_ctx* ctx, const float* xyz, int n, const double* R_level9, int top_k,
+                         const vg_reloc_params* prm, int install, double* out_pose, vg_pose_score* out_score,
+                         vg_place_candidate* out_place, int* ok);
+
 /* ---- Map views: many sensors in one frozen map ------------------------------
  * vg_map_attach makes `tracker` a read-only view of `owner`'s map: every kernel
  * of the tracker that reads the map (the IEKF, vg_score_poses, vg_relocalize,

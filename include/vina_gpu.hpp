@@ -173,6 +173,44 @@ class LioCore {
   }
   void change_clear() { check(vg_change_clear(ctx_), "vg_change_clear"); }
   void change_end() { check(vg_change_end(ctx_), "vg_change_end"); }
+  // the place index (vina_gpu.h "Place index"): build / end on the map's owner; info, scan, query and
+  // relocalize_global on the owner or any tracker attached to it. R_level9 null: the current R
+  void places_build(const double* positions, int M, const vg_places_params* prm = nullptr) {
+    check(vg_places_build(ctx_, positions, M, prm), "vg_places_build");
+  }
+  struct PlacesInfo {
+    int M = 0, n_valid = 0;
+    std::vector<int32_t> hit_bins;
+  };
+  PlacesInfo places_info() {
+    PlacesInfo r;
+    check(vg_places_info(ctx_, &r.M, &r.n_valid, nullptr, nullptr), "vg_places_info");
+    r.hit_bins.resize((size_t)r.M);
+    check(vg_places_info(ctx_, &r.M, &r.n_valid, nullptr, r.hit_bins.data()), "vg_places_info");
+    return r;
+  }
+  // desc / n_per_bin: n_el * n_az entries each, either may be null
+  void places_scan(const float* xyz, int n, const double* R_level9, uint16_t* desc, int32_t* n_per_bin) {
+    check(vg_places_scan(ctx_, xyz, n, R_level9, desc, n_per_bin), "vg_places_scan");
+  }
+  std::vector<vg_place_candidate> places_query(const float* xyz, int n, const double* R_level9 = nullptr,
+                                               int top_k = 16, int32_t* scores_all = nullptr) {
+    std::vector<vg_place_candidate> out((size_t)(top_k > 0 ? top_k : 0));
+    int n_out = 0;
+    check(vg_places_query(ctx_, xyz, n, R_level9, top_k, out.data(), &n_out, scores_all), "vg_places_query");
+    out.resize((size_t)n_out);
+    return out;
+  }
+  void places_end() { check(vg_places_end(ctx_), "vg_places_end"); }
+  // returns ok; prm null: the default window around each candidate; score / place may be null
+  bool relocalize_global(const float* xyz, int n, const double* R_level9, int top_k, const vg_reloc_params* prm,
+                         bool install, double* out_pose, vg_pose_score* score = nullptr,
+                         vg_place_candidate* place = nullptr) {
+    int ok = 0;
+    check(vg_relocalize_global(ctx_, xyz, n, R_level9, top_k, prm, install ? 1 : 0, out_pose, score, place, &ok),
+          "vg_relocalize_global");
+    return ok != 0;
+  }
   // map views (vina_gpu.h "Map views"): this context reads owner's frozen map. The owner
   // must outlive its views: destroy (or detach) the trackers first
   void attach(LioCore& owner) { check(vg_map_attach(ctx_, owner.ctx_), "vg_map_attach"); }

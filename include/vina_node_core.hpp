@@ -149,9 +149,14 @@ class NodeCore {
         continue;
       }
       Scan& sc = it->second;
-      if (reloc_armed_) {  // the first scan after load_map: its pose in the map, from the guess
+      if (reloc_armed_) {  // the first scan after load_map: its pose in the map, from the guess or the place index
         double pose[12];
-        reloc_ok_ = lio_.relocalize(sc.xyz.data(), (int)sc.inten.size(), reloc_guess_, reloc_prm_, true, pose, nullptr);
+        if (reloc_global_)
+          reloc_ok_ = lio_.relocalize_global(sc.xyz.data(), (int)sc.inten.size(), reloc_level_set_ ? reloc_guess_ : nullptr,
+                                             reloc_top_k_, reloc_prm_set_ ? &reloc_prm_ : nullptr, true, pose, nullptr,
+                                             &reloc_place_);
+        else
+          reloc_ok_ = lio_.relocalize(sc.xyz.data(), (int)sc.inten.size(), reloc_guess_, reloc_prm_, true, pose, nullptr);
         reloc_armed_ = false;
         reloc_done_ = true;
       }
@@ -216,9 +221,25 @@ class NodeCore {
   void relocalize(const double guess_pose[12], const vg_reloc_params& prm) {
     for (int k = 0; k < 12; k++) reloc_guess_[k] = guess_pose[k];
     reloc_prm_ = prm;
+    reloc_global_ = false;
     reloc_armed_ = true;
     reloc_done_ = false;
   }
+  // The same without a position: the first scan stepped after it is relocalised through the place
+  // index of the map (vg_relocalize_global, install = 1; lio().places_build first). R_level9: a
+  // rotation with the sensor's roll and pitch, null: the state's R at that scan; prm null: the
+  // default window around each candidate. relocalize_place() is the winning candidate.
+  void relocalize_global(const double* R_level9 = nullptr, int top_k = 16, const vg_reloc_params* prm = nullptr) {
+    reloc_level_set_ = R_level9 != nullptr;
+    for (int k = 0; k < 9 && R_level9; k++) reloc_guess_[k] = R_level9[k];
+    reloc_prm_set_ = prm != nullptr;
+    if (prm) reloc_prm_ = *prm;
+    reloc_top_k_ = top_k;
+    reloc_global_ = true;
+    reloc_armed_ = true;
+    reloc_done_ = false;
+  }
+  const vg_place_candidate& relocalize_place() const { return reloc_place_; }
   bool relocalized() const { return reloc_done_; }
   bool relocalize_ok() const { return reloc_ok_; }
   // called after every stepped scan, before the next is taken: the caller reads what belongs to
@@ -382,6 +403,9 @@ class NodeCore {
   bool reloc_armed_ = false, reloc_done_ = false, reloc_ok_ = false;
   double reloc_guess_[12] = {};
   vg_reloc_params reloc_prm_ = {};
+  bool reloc_global_ = false, reloc_level_set_ = false, reloc_prm_set_ = false;
+  int reloc_top_k_ = 16;
+  vg_place_candidate reloc_place_ = {};
   int publish_ = 0;  // vg_set_publish flags
   bool visualization_ = false;
   std::function<void()> after_step_;

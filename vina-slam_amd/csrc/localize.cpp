@@ -232,6 +232,20 @@ bool solve6(const double* hth, const double* b, double* x) {
   return true;
 }
 
+bool reloc_better(const vg_pose_score& a, const vg_pose_score& b) { return better(a, b); }
+
+// x_curr takes the pose with the initial covariance; v, bg, ba and g stay
+int reloc_install(vg_ctx* ctx, const double* pose12) {
+  HX& x = hp(ctx)->x_curr;
+  memcpy(x.R.a, pose12, 72);
+  memcpy(x.p.a, pose12 + 9, 24);
+  x.cov = HX().cov;  // the initial covariance (imu_ekf.cpp)
+  double blk[kXC];
+  hx_put_block(x, blk);  // the device's copy too (a scan that propagates on the device starts from it)
+  VG_HIP(hipMemcpy(ctx->st->xc, blk, sizeof(blk), hipMemcpyHostToDevice));
+  return VG_OK;
+}
+
 int host_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess, const vg_reloc_params* prm,
                     int install, double* out_pose, vg_pose_score* out_score, int* ok) {
   HostPipe* P = hp(ctx);
@@ -309,15 +323,7 @@ int host_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess, c
   memcpy(out_pose, best_pose, sizeof(best_pose));
   if (out_score) *out_score = best;
   *ok = good ? 1 : 0;
-  if (good && install) {
-    HX& x = P->x_curr;
-    memcpy(x.R.a, best_pose, 72);
-    memcpy(x.p.a, best_pose + 9, 24);
-    x.cov = HX().cov;  // the initial covariance (imu_ekf.cpp)
-    double blk[kXC];
-    hx_put_block(x, blk);  // the device's copy too (a scan that propagates on the device starts from it)
-    VG_HIP(hipMemcpy(ctx->st->xc, blk, sizeof(blk), hipMemcpyHostToDevice));
-  }
+  if (good && install) VG_TRY(reloc_install(ctx, best_pose));
   return VG_OK;
 }
 

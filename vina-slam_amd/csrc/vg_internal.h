@@ -436,6 +436,30 @@ struct ChangeLayer {
   void* d_out = nullptr; // the report's record staging, grown on demand
   size_t out_bytes = 0;
 };
+// The place index (vina_gpu.h "Place index"; places.hip, places_host.cpp): a side
+// structure of the context that owns a frozen map, like the change layer. One
+// query at a time (vg_ctx::places_mu of the owner): the scan's histogram, its
+// descriptor and the match's results are the index's own scratch.
+struct PlaceIndex {
+  vg_places_params prm;       // as vg_places_build was given them (zeros: the defaults)
+  int M = 0, A = 0, E = 0, n_valid = 0;
+  double frame[9];            // rows ex, ey, up
+  double spacing = 0.0;       // median nearest-neighbour distance of the places in the ex-ey plane (0: M == 1)
+  std::vector<double> pos;    // M x 3, as given
+  std::vector<int> hit;       // per place: its hit bins
+  double* d_pos = nullptr;    // M x 3
+  double* d_dirs = nullptr;   // A E x 3, world
+  uint16_t* d_desc = nullptr; // M x E x A
+  int* d_hit = nullptr;       // M
+  unsigned long long* d_sum = nullptr;  // A E: the scan's sums of q
+  unsigned* d_cnt = nullptr;  // A E: its points per bin
+  uint16_t* d_scan = nullptr; // A E: its descriptor
+  int* d_scan_valid = nullptr;  // its non-empty bins
+  int* d_best = nullptr;      // M x 4: best shift, its score, second shift, its score
+  int* d_scores = nullptr;    // M x A, allocated on the first request
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the build's kernel; around the last query's
+  bool queried = false;       // ev[2], ev[3] have been recorded
+};
 // window view for the map kernels, built on the device from DState::xs
 struct WinArg {
   int mp[kMaxWin];      // mp[] ring (octree.cpp:75)
@@ -567,6 +591,8 @@ struct vg_ctx {
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
+  vg::PlaceIndex* places = nullptr;  // the place index of this context's map (vg_places_build .. vg_places_end)
+  std::mutex places_mu;      // the same discipline for `places`
   vg_stats stats;
   void* host = nullptr;     // host-side pipeline state (HostPipe, vg_host.h)
   // stage timing with HIP events on the context stream (vg_profile)
@@ -967,6 +993,16 @@ int change_accum_dev(vg_ctx* ctx, ChangeLayer* L, const MP& mp, const float* x, 
 // every selected record, in report order; tot4: points dropped, out of range, nodes touched, cells used
 int change_report_dev(vg_ctx* ctx, ChangeLayer* L, const vg_change_query& q, std::vector<vg_change_leaf>& leaves,
                       std::vector<vg_change_cell>& cells, long long* tot4);
+// places.hip: the place index's device side. The caller holds the owner's places_mu and has drained ctx's stream
+int places_prm_ok(const vg_places_params* prm, int* A, int* E);  // VG_E_ARG: a limit exceeded, a bad span
+int places_dirs(const vg_places_params* prm, double* out, int cap, int* count);
+int places_build_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp);  // I->prm, pos, frame, M set: allocates, casts, reads hit
+void places_free(PlaceIndex* I);
+// the scan's descriptor into I->d_scan through ctx's staging and stream; desc / n_per_bin: host copies or null
+int places_scan_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp, const float* xyz, int n, const double* R_level9,
+                    uint16_t* desc, int32_t* n_per_bin, int* n_valid);
+// I->d_scan against every place: best (M x 4 ints, host), scores_all (M x A, host) or null
+int places_match_dev(vg_ctx* ctx, PlaceIndex* I, int* best, int32_t* scores_all);
 // raycast_host.cpp: the two calls behind the C-ABI
 int host_raycast(vg_ctx* ctx, const double* origins, int n_origins, const double* dirs, int n,
                  const vg_ray_params* prm, vg_ray_hit* out);
@@ -989,10 +1025,17 @@ inline int refuse_owner(vg_ctx* ctx, const char* who) {
   return VG_E_STATE;
 }
 // what a change layer rules out on its owner (vina_gpu.h "Change layer"): node ids must not move, the map not change
-inline int refuse_layer(vg_ctx* ctx, const char* who) {
-  if (!ctx->change) return VG_OK;
-  ctx->err = std::string(who) + ": the context's map has a change layer (vg_change_end first)";
-  return VG_E_STATE;
+// ... and a place index, whose rows are the map's ranges (places = false: the caller ends the index itself)
+inline int refuse_layer(vg_ctx* ctx, const char* who, bool places = true) {
+  if (ctx->change) {
+    ctx->err = std::string(who) + ": the context's map has a change layer (vg_change_end first)";
+    return VG_E_STATE;
+  }
+  if (places && ctx->places) {
+    ctx->err = std::string(who) + ": the context's map has a place index (vg_places_end first)";
+    return VG_E_STATE;
+  }
+  return VG_OK;
 }
 inline int refuse_fleet(vg_ctx* ctx, const char* who) {
   if (!ctx->fleet) return VG_OK;
@@ -1019,6 +1062,8 @@ int host_score_poses(vg_ctx* ctx, const float* xyz, int n, const double* poses, 
                      vg_pose_score* out, void* per_point);
 int host_relocalize(vg_ctx* ctx, const float* xyz, int n, const double* guess, const vg_reloc_params* prm,
                     int install, double* out_pose, vg_pose_score* out_score, int* ok);
+bool reloc_better(const vg_pose_score& a, const vg_pose_score& b);  // vg_relocalize's ranking
+int reloc_install(vg_ctx* ctx, const double* pose12);               // ... and what its install does
 int host_quiesce(vg_ctx* ctx);  // host_sync between scans; inside an open scan the context stream's drain
 int host_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters);  // kdlio_host.cpp
 int decode_scan(vg_ctx* ctx, const void* records, int n, const vg_lidar_format* fmt, float* xyz, float* inten,

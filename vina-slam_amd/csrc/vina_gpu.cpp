@@ -310,8 +310,9 @@ int vg_destroy(vg_ctx* ctx) {
   if (!ctx) return VG_OK;
   // a map other contexts read, or a fleet's tracker, stays; a tracker lets go of the owner's map first
   VG_TRY(refuse_owner(ctx, "vg_destroy"));
-  VG_TRY(refuse_layer(ctx, "vg_destroy"));
+  VG_TRY(refuse_layer(ctx, "vg_destroy", false));
   VG_TRY(refuse_fleet(ctx, "vg_destroy"));
+  if (ctx->places) (void)vg_places_end(ctx);  // (no tracker reads it: the owner has no views)
   if (ctx->view_of) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->map = ctx->own_map;

@@ -14,13 +14,21 @@
 //
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
-//        [--map FILE --localize [--guess "x y z yaw"] [--scan-diff] [--changes FILE [--changes-scans FILE]]]
+//        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff]
+//         [--changes FILE [--changes-scans FILE]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
 // --map FILE --localize: load the map FILE (a checkpoint), relocalise on the first scan around the
 // guess (default: the map's saved pose; --guess: position and yaw about z, the saved roll / pitch kept;
 // window +-2 m / 0.25 m, +-30 deg / 2.5 deg) and run with the map frozen; the TUM output is as always.
+// --global (with --localize, not with --guess): no position is assumed. A place index (vg_places_build) is
+// built from the map's own path rows, which the checkpoint carries — the LiDAR origins p + R ext_t, thinned to
+// at least S metres apart (--places-step, default 1) — or, where the map has fewer than two rows, on a lattice of
+// step S over the bounds of its plane leaves' voxel centres at the saved pose's height; the first scan is
+// relocalised through it (vg_relocalize_global) with the saved attitude as R_level, and
+//   relocalise: global place <i> yaw <deg> score <s>
+// goes to stderr beside the relocalise line. The index is ended once the scan is placed.
 // --scan-diff (with --localize): every localised scan's downsampled cloud is checked against the map at
 // its IEKF pose (vg_scan_diff) and one line per scan goes to stdout ahead of the summary line:
 //   scan_diff <scan index> <scan end time> <n_ds> <unknown> <consistent> <appeared> <vanished>
@@ -47,7 +55,8 @@ int main(int argc0, char** argv0) {
   std::vector<char*> pos;
   std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans;
   int ck_at = -1;
-  bool localize = false, scan_diff = false;
+  bool localize = false, scan_diff = false, global = false;
+  double places_step = 1.0;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
     if (i + 1 < argc0 && a == "--checkpoint-out") ck_out = argv0[++i];
@@ -57,7 +66,9 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--guess") guess_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--changes") changes_file = argv0[++i];
     else if (i + 1 < argc0 && a == "--changes-scans") changes_scans = argv0[++i];
+    else if (i + 1 < argc0 && a == "--places-step") places_step = atof(argv0[++i]);
     else if (a == "--localize") localize = true;
+    else if (a == "--global") global = true;
     else if (a == "--scan-diff") scan_diff = true;
     else pos.push_back(argv0[i]);
   }
@@ -66,6 +77,10 @@ int main(int argc0, char** argv0) {
   const bool changes = !changes_file.empty();
   if ((scan_diff || changes) && !localize) {
     fprintf(stderr, "%s: --scan-diff and --changes need --map FILE --localize\n", argv0[0]);
+    return 2;
+  }
+  if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
+    fprintf(stderr, "%s: --global needs --map FILE --localize, a positive --places-step, and no --guess\n", argv0[0]);
     return 2;
   }
   if (!changes_scans.empty() && !changes) {
@@ -147,11 +162,52 @@ int main(int argc0, char** argv0) {
         memcpy(g, R2, sizeof(R2));
         g[9] = x, g[10] = y, g[11] = z;
       }
-      vg_reloc_params prm;
-      memset(&prm, 0, sizeof(prm));
-      prm.half_xy = 2.0, prm.step_xy = 0.25;
-      prm.half_yaw = 30 * M_PI / 180, prm.step_yaw = 2.5 * M_PI / 180;
-      node.relocalize(g, prm);
+      if (global) {
+        std::vector<double> places;
+        vg_ctx* c = node.lio().raw();
+        int rows = 0;
+        if (vg_path(c, nullptr, 0, &rows) != VG_OK) return 1;
+        if (rows >= 2) {
+          std::vector<double> path((size_t)rows * 14);
+          if (vg_path(c, path.data(), rows, &rows) != VG_OK) return 1;
+          for (int r = 0; r < rows; r++) {
+            const double* R = &path[(size_t)r * 14 + 1];
+            const double* p = R + 9;
+            double o[3];
+            for (int j = 0; j < 3; j++)
+              o[j] = p[j] + R[3 * j] * cfg.ext_t[0] + R[3 * j + 1] * cfg.ext_t[1] + R[3 * j + 2] * cfg.ext_t[2];
+            const size_t m = places.size();
+            if (m == 0 || hypot(hypot(o[0] - places[m - 3], o[1] - places[m - 2]), o[2] - places[m - 1]) >= places_step)
+              places.insert(places.end(), o, o + 3);
+          }
+        } else {
+          const std::vector<vg_plane_marker> pl = node.lio().map_planes();
+          if (pl.empty()) {
+            fprintf(stderr, "vg_node_replay: --global: the map has neither path rows nor planes\n");
+            return 1;
+          }
+          double lo[2] = {pl[0].voxel_center[0], pl[0].voxel_center[1]}, hi[2] = {lo[0], lo[1]};
+          for (const vg_plane_marker& m : pl)
+            for (int j = 0; j < 2; j++) {
+              lo[j] = m.voxel_center[j] < lo[j] ? m.voxel_center[j] : lo[j];
+              hi[j] = m.voxel_center[j] > hi[j] ? m.voxel_center[j] : hi[j];
+            }
+          for (double y = lo[1]; y <= hi[1] + 1e-9; y += places_step)
+            for (double x = lo[0]; x <= hi[0] + 1e-9; x += places_step) {
+              const double o[3] = {x, y, g[11]};
+              places.insert(places.end(), o, o + 3);
+            }
+        }
+        node.lio().places_build(places.data(), (int)(places.size() / 3));
+        fprintf(stderr, "places: %d from %s\n", (int)(places.size() / 3), rows >= 2 ? "the map's path" : "a lattice");
+        node.relocalize_global(g, 16, nullptr);  // R_level: the saved attitude
+      } else {
+        vg_reloc_params prm;
+        memset(&prm, 0, sizeof(prm));
+        prm.half_xy = 2.0, prm.step_xy = 0.25;
+        prm.half_yaw = 30 * M_PI / 180, prm.step_yaw = 2.5 * M_PI / 180;
+        node.relocalize(g, prm);
+      }
     }
     // --scan-diff / --changes: after every localised scan, its downsampled cloud against the map at its IEKF pose
     FILE* fscans = nullptr;
@@ -212,6 +268,11 @@ int main(int argc0, char** argv0) {
       n_step += node.spin();
       if (localize && node.relocalized() && !reloc_said) {
         fprintf(stderr, "relocalise: %s\n", node.relocalize_ok() ? "ok" : "failed (the guess's pose stays)");
+        if (global) {
+          const vg_place_candidate& pc = node.relocalize_place();
+          fprintf(stderr, "relocalise: global place %d yaw %.3f score %d\n", pc.place, pc.yaw * 180.0 / M_PI, pc.score);
+          node.lio().places_end();  // (a later --checkpoint-out would be refused while it stands)
+        }
         reloc_said = true;
       }
       if (ck_at >= 0 && node.packages() >= ck_at) {

@@ -137,6 +137,52 @@ class ChangeTotals(ctypes.Structure):
                 ("leaves_touched", ctypes.c_int64), ("reserved", ctypes.c_int64 * 6)]
 
 
+class PlacesParams(ctypes.Structure):
+    """vg_places_params, 144 bytes."""
+    _fields_ = [("n_az", ctypes.c_int), ("n_el", ctypes.c_int), ("el_min", ctypes.c_double),
+                ("el_max", ctypes.c_double), ("t_max", ctypes.c_double), ("clip", ctypes.c_double),
+                ("min_bins", ctypes.c_int), ("pad", ctypes.c_int), ("ray", RayParams),
+                ("reserved", ctypes.c_double * 4)]
+
+
+# vg_place_candidate (48 bytes)
+PLACE_CANDIDATE_DTYPE = np.dtype([("place", "<i4"), ("shift", "<i4"), ("score", "<i4"), ("n_valid", "<i4"),
+                                  ("pos", "<f8", 3), ("yaw", "<f8")])
+PLACE_NONE = 2 ** 31 - 1  # an invalid place's score
+
+
+def places_params(n_az=0, n_el=0, el_min=0.0, el_max=0.0, t_max=0.0, clip=0.0, min_bins=0, **ray):
+    """vg_places_params; zeros take the defaults (120 x 12 bins, -+30 degrees, 60 m, clip 2 m, n_az n_el / 8)."""
+    p = PlacesParams()
+    p.n_az, p.n_el, p.el_min, p.el_max, p.t_max, p.clip, p.min_bins = n_az, n_el, el_min, el_max, t_max, clip, min_bins
+    p.ray = ray_params(**ray)
+    return p
+
+
+def places_dirs(**params):
+    """vg_places_dirs: the bin-centre directions (n_el * n_az, 3), entry e * n_az + a, in the descriptor's frame
+    (no device). Raises VgError (-1) where a limit is exceeded."""
+    p = places_params(**params)
+    n = ctypes.c_int(0)
+    r = lib().vg_places_dirs(ctypes.byref(p), None, 0, ctypes.byref(n))
+    if r != 0:
+        raise VgError("vg_places_dirs failed (%d)" % r)
+    out = np.zeros((n.value, 3))
+    r = lib().vg_places_dirs(ctypes.byref(p), _d(out), n.value, ctypes.byref(n))
+    if r != 0:
+        raise VgError("vg_places_dirs failed (%d)" % r)
+    return out
+
+
+def place_lattice(lo, hi, step, z):
+    """(M, 3) positions on a lattice over [lo[0], hi[0]] x [lo[1], hi[1]] (both ends where the step fits) at
+    height z, x fastest: sample positions for Context.places_build."""
+    nx = int(np.floor((hi[0] - lo[0]) / step + 1e-9)) + 1
+    ny = int(np.floor((hi[1] - lo[1]) / step + 1e-9)) + 1
+    gx, gy = np.meshgrid(lo[0] + step * np.arange(nx), lo[1] + step * np.arange(ny), indexing="xy")
+    return np.stack([gx.reshape(-1), gy.reshape(-1), np.full(nx * ny, float(z))], axis=1)
+
+
 # vg_change_leaf (112 bytes) and vg_change_cell (56 bytes) as numpy record types
 CHANGE_LEAF_DTYPE = np.dtype([("node", "<i4"), ("layer", "<i4"), ("n_consistent", "<i4"), ("n_vanished", "<i4"),
                               ("n_occluded", "<i4"), ("n_scans", "<i4"), ("flags", "<i4"), ("pad", "<i4"),
@@ -318,6 +364,18 @@ def lib():
                                            ctypes.POINTER(ChangeTotals)]
             L.vg_change_clear.argtypes = [P]
             L.vg_change_end.argtypes = [P]
+        L.has_places = hasattr(L, "vg_places_build")  # a build older than the place index (A/B runs)
+        if L.has_places:
+            pp = ctypes.POINTER(PlacesParams)
+            L.vg_places_dirs.argtypes = [pp, dp, ctypes.c_int, ip]
+            L.vg_places_build.argtypes = [P, dp, ctypes.c_int, pp]
+            L.vg_places_info.argtypes = [P, ip, ip, P, P]
+            L.vg_places_scan.argtypes = [P, fp, ctypes.c_int, dp, P, P]
+            L.vg_places_query.argtypes = [P, fp, ctypes.c_int, dp, ctypes.c_int, P, ip, P]
+            L.vg_places_end.argtypes = [P]
+            L.vg_relocalize_global.argtypes = [P, fp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(RelocParams),
+                                               ctypes.c_int, dp, ctypes.POINTER(PoseScore), P, ip]
+            L.vgx_places_ms.argtypes = [P, dp, dp]
         L.vg_trajectory.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_path.argtypes = [P, dp, ctypes.c_int, ip]
         L.vg_poll.argtypes = [P, ip, ip, ip]
@@ -398,6 +456,7 @@ class Context:
         if r != 0:
             raise VgError("vg_create failed (%d)" % r)
         self._fn_step = lib().vg_step_dev
+        self._cfg = cconfig
 
     def _chk(self, r, what):
         if r != 0:
@@ -704,6 +763,105 @@ class Context:
     def change_end(self):
         """vg_change_end: the layer freed."""
         self._chk(lib().vg_change_end(self.h), "vg_change_end")
+
+    # ---- the place index (vina_gpu.h "Place index")
+    def places_build(self, positions, **params):
+        """vg_places_build on the context that owns a frozen map: positions (M, 3), LiDAR origins in the
+        world; params: places_params. Replaces an existing index."""
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        p = places_params(**params)
+        self._chk(lib().vg_places_build(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0], ctypes.byref(p)),
+                  "vg_places_build")
+        self._places_shape = (p.n_el or 12, p.n_az or 120)
+
+    def _places_bins(self):
+        o = getattr(self, "_owner", None) or self
+        return getattr(o, "_places_shape", (12, 120))
+
+    def places_info(self, desc=False):
+        """vg_places_info: {M, n_valid, hit_bins (M,)} and, with desc, the descriptors (M, n_el, n_az) uint16."""
+        m, nv = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(lib().vg_places_info(self.h, ctypes.byref(m), ctypes.byref(nv), None, None), "vg_places_info")
+        E, A = self._places_bins()
+        hit = np.zeros(max(m.value, 1), dtype=np.int32)
+        d = np.zeros((max(m.value, 1), E, A), dtype=np.uint16) if desc else None
+        self._chk(lib().vg_places_info(self.h, ctypes.byref(m), ctypes.byref(nv), None if d is None else d.ctypes.data,
+                                       hit.ctypes.data), "vg_places_info")
+        out = {"M": m.value, "n_valid": nv.value, "hit_bins": hit[: m.value]}
+        if desc:
+            out["desc"] = d[: m.value]
+        return out
+
+    def places_scan(self, xyz, R_level=None):
+        """vg_places_scan: the scan's descriptor (n_el, n_az) uint16 and its points per bin (int32). R_level:
+        (3, 3) or (9,), a rotation with the sensor's roll and pitch; None: the context's current R."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        R = None if R_level is None else np.ascontiguousarray(R_level, dtype=np.float64).reshape(9)
+        E, A = self._places_bins()
+        d = np.zeros((E, A), dtype=np.uint16)
+        n = np.zeros((E, A), dtype=np.int32)
+        self._chk(lib().vg_places_scan(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                       None if R is None else _d(R), d.ctypes.data, n.ctypes.data), "vg_places_scan")
+        return d, n
+
+    def places_query(self, xyz, R_level=None, top_k=16, scores=False):
+        """vg_places_query: the candidates (PLACE_CANDIDATE_DTYPE, ascending score, then place, then shift);
+        with scores also the full (M, n_az) int32 table (PLACE_NONE rows for invalid places)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        R = None if R_level is None else np.ascontiguousarray(R_level, dtype=np.float64).reshape(9)
+        out = np.zeros(max(top_k, 1), dtype=PLACE_CANDIDATE_DTYPE)
+        n = ctypes.c_int(0)
+        sc = None
+        if scores:
+            sc = np.zeros((self.places_info()["M"], self._places_bins()[1]), dtype=np.int32)
+        self._chk(lib().vg_places_query(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                        None if R is None else _d(R), top_k, out.ctypes.data, ctypes.byref(n),
+                                        None if sc is None else sc.ctypes.data), "vg_places_query")
+        return (out[: n.value], sc) if scores else out[: n.value]
+
+    def places_end(self):
+        """vg_places_end: the index freed."""
+        self._chk(lib().vg_places_end(self.h), "vg_places_end")
+
+    def places_from_path(self, spacing, **params):
+        """Build the index from this context's own path rows (vg_path): the LiDAR origins p + R ext_t of
+        the rows (ext_t: the configuration's), thinned so that every kept origin is at least `spacing`
+        from the one kept before it. Returns the positions used."""
+        ext_t = np.array(list(self._cfg.ext_t), dtype=np.float64)
+        rows = self.path()
+        keep = []
+        for row in rows:
+            o = row[10:13] + row[1:10].reshape(3, 3) @ ext_t
+            if not keep or np.linalg.norm(o - keep[-1]) >= spacing:
+                keep.append(o)
+        pos = np.array(keep).reshape(-1, 3)
+        self.places_build(pos, **params)
+        return pos
+
+    def relocalize_global(self, xyz, R_level=None, top_k=16, install=False, **params):
+        """vg_relocalize_global: (pose (12,), the refined winner's record, the winning candidate
+        (PLACE_CANDIDATE_DTYPE scalar), ok). No params: the default window around each candidate
+        (half the places' spacing, +-1.5 azimuth bins); else reloc_params."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        R = None if R_level is None else np.ascontiguousarray(R_level, dtype=np.float64).reshape(9)
+        p = reloc_params(**params) if params else None
+        pose = np.zeros(12)
+        sc = PoseScore()
+        cand = np.zeros(1, dtype=PLACE_CANDIDATE_DTYPE)
+        ok = ctypes.c_int(0)
+        self._chk(lib().vg_relocalize_global(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                             None if R is None else _d(R), top_k,
+                                             None if p is None else ctypes.byref(p), 1 if install else 0, _d(pose),
+                                             ctypes.byref(sc), cand.ctypes.data, ctypes.byref(ok)),
+                  "vg_relocalize_global")
+        rec = {"matches": sc.matches, "in_map": sc.in_map, "cost": sc.cost, "sum_abs": sc.sum_abs, "nn": list(sc.nn)}
+        return pose, rec, cand[0], bool(ok.value)
+
+    def places_ms(self):
+        """Device time (ms) of the index's build kernel and of the last query's kernels (HIP events)."""
+        a, b = ctypes.c_double(0), ctypes.c_double(0)
+        self._chk(lib().vgx_places_ms(self.h, ctypes.byref(a), ctypes.byref(b)), "vgx_places_ms")
+        return a.value, b.value
 
     def ray_ms(self):
         """Device time of the last raycast slab's / scan_diff call's kernels (HIP events on the context stream), ms."""
