@@ -477,6 +477,85 @@ typedef struct vg_diff_summary {
 int vg_scan_diff(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* prm,
                  vg_diff_point* per_point, vg_diff_summary* out);
 
+/* ---- Localisability: expected pose information ---------------------------------
+ * How well the map constrains a pose: the 6 x 6 point-to-plane information
+ * matrix, summed per place over the range image the map shows from there
+ * (vg_localizability), and summed over a measured scan's consistent points at a
+ * pose (vg_scan_info). Both read the map only and keep no state.
+ *
+ * The per-ray term. A ray from origin o along the unit direction d with the hit m
+ * at range r, n = m.normal as stored, c = |m.ndotd|:
+ *   J  = [n ; (r d) x n]   (6 entries): the derivative of the residual n.(h -
+ *        centre), h = o + r d, under o -> o + dp, d -> Exp(dtheta) d. The
+ *        unknowns are ordered [dp, dtheta], in the world frame, rotation about o;
+ *   s2 = c^2 (m.var + dept_err^2 + (r sin(beam_err deg))^2 (1 - c^2) / c^2) +
+ *        floor_var   (the bracket is gate^2 / gate_sigma^2 of vg_scan_diff);
+ *   w  = 1 / s2.
+ * The ray contributes w J J^T and counts as a hit only if m is a hit and s2 is
+ * finite and > 0. The 21 unique entries of H and sum_w are accumulated in f64.
+ *
+ * The record. H: row-major, symmetric, both triangles filled with the same bits.
+ * With H = [H_pp H_pt; H_tp H_tt] (p translation, t rotation), S_t = H_pp - H_pt
+ * H_tt^-1 H_tp is the translation information with the rotation marginalised and
+ * S_r = H_tt - H_tp H_pp^-1 H_pt its mirror image. eig_t / eig_r: their
+ * eigenvalues in ascending order; dir_t / dir_r: the unit eigenvector of the
+ * smallest one, its sign chosen so that its largest-magnitude component (the
+ * first of equals) is positive. flags:
+ *   bit 0 valid: n_hits >= min_hits. An invalid record carries its H, sum_w and
+ *     counts; its eig and dir are zero and bits 1 and 2 are clear;
+ *   bit 1 the rotation block is degenerate: the eigenvalues of H_tt have
+ *     lambda_min <= 1e-12 lambda_max. Then S_t = H_pp is reported unmarginalised
+ *     and eig_r / dir_r are zero;
+ *   bit 2 the same for the translation block (H_pp; S_r = H_tt, eig_t / dir_t
+ *     zero). Where both blocks are degenerate both bits are set and bit 1's rule
+ *     holds: eig_t / dir_t are H_pp's, eig_r / dir_r zero;
+ *   bit 3 some ray ended truncated or left the key range (VG_RAY_TRUNCATED,
+ *     VG_RAY_LEFT_RANGE). */
+typedef struct vg_info_params {
+  vg_ray_params ray;     /* vg_localizability's rays; vg_scan_info casts with diff->ray */
+  double floor_var;      /* m^2 added to every s2; default 0 */
+  int    min_hits;       /* <= 0: 16 */
+  int    pad;
+  double reserved[4];
+} vg_info_params;
+typedef struct vg_info_rec {   /* 416 bytes, no implicit padding */
+  double  H[36];
+  double  eig_t[3], eig_r[3];
+  double  dir_t[3], dir_r[3];
+  double  sum_w, reserved;     /* sum of w over the hits */
+  int32_t n_rays, n_hits;      /* rays cast (D; a scan's n); contributing rays */
+  int32_t flags, pad;
+} vg_info_rec;
+#define VG_INFO_VALID 1
+#define VG_INFO_ROT_DEGENERATE 2
+#define VG_INFO_TRANS_DEGENERATE 4
+#define VG_INFO_RAY_ENDED 8
+/* One record per place. positions: M x 3 doubles, LiDAR origins in the world.
+ * dirs: D x 3 doubles, world-frame directions shared by all places, 1 <= D <=
+ * 4096 (vg_places_dirs gives a suitable set; normalised on the device). prm: NULL
+ * for the defaults. out: M records. A zero or non-finite direction or origin is
+ * an invalid ray (VG_RAY_INVALID) and contributes nothing. The sums are reduced
+ * in an order that is a function of D alone, so a place's record has the same
+ * bytes at any M, at any position in `positions` and in any call; M is walked
+ * in slabs, the staging allocated on the first call. Only the records leave the
+ * device. M == 0 is fine. NULL ctx, dirs, or (M > 0) positions / out, M < 0, D
+ * outside [1, 4096]: VG_E_ARG. Legal where vg_raycast is: completes outstanding
+ * work first; mapping on or off; on an owner, an attached tracker and a fleet's
+ * tracker; unsharded contexts only (VG_E_STATE with world > 1). */
+int vg_localizability(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
+                      const vg_info_params* prm, vg_info_rec* out);
+/* One record for a measured scan at a pose: xyz, n, pose12 and diff as
+ * vg_scan_diff takes them (pose12 NULL: the context's current state; diff NULL:
+ * the defaults), and every point classified exactly as vg_scan_diff does. Only the
+ * CONSISTENT points contribute, with o the sensor origin, r d = w - o (the
+ * measured point) and the hit's n, c and var. n_rays = n, n_hits the contributing
+ * points. Every workgroup reduces its 256 points in a fixed tree and one workgroup
+ * adds the partial sums in block order: the record depends on the input and its
+ * order alone. n == 0 gives a zero record. Arguments in error and where it is
+ * legal: as vg_scan_diff. */
+int vg_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* diff,
+                 const vg_info_params* prm, vg_info_rec* out);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

@@ -140,6 +140,20 @@ class LioCore {
     check(vg_scan_diff(ctx_, xyz, n, pose12, prm, per_point, &out), "vg_scan_diff");
     return out;
   }
+  // localisability (vina_gpu.h "Localisability"): one record per place over the shared D directions
+  std::vector<vg_info_rec> localizability(const double* positions, int M, const double* dirs, int D,
+                                          const vg_info_params* prm = nullptr) {
+    std::vector<vg_info_rec> out((size_t)(M > 0 ? M : 0));
+    check(vg_localizability(ctx_, positions, M, dirs, D, prm, out.data()), "vg_localizability");
+    return out;
+  }
+  // a measured scan's record at pose12 (null: the current state); diff / prm null: the defaults
+  vg_info_rec scan_info(const float* xyz, int n, const double* pose12 = nullptr, const vg_diff_params* diff = nullptr,
+                        const vg_info_params* prm = nullptr) {
+    vg_info_rec out;
+    check(vg_scan_info(ctx_, xyz, n, pose12, diff, prm, &out), "vg_scan_info");
+    return out;
+  }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
   // owner or any tracker attached to it; prm / q null: the defaults
   void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }

@@ -36,12 +36,14 @@ inline DiffPrm diff_prm(const vg_diff_params* p) {
 }
 
 // pb: the point in the LiDAR frame. dp: its record; av: |range - r| where
-// consistent, else 0; rflags: the ray's flags; w: the point in the world
+// consistent, else 0; rflags: the ray's flags; w: the point in the world;
+// o, h: the sensor origin and the beam's hit record (vg_info.h sums over them)
 __device__ __forceinline__ void diff_point(const MP& mp, const DevMap& m, const V3& pb, const Pose12& pose,
-                                           const DiffPrm& prm, vg_diff_point& dp, double& av, int& rflags, V3& w) {
+                                           const DiffPrm& prm, vg_diff_point& dp, double& av, int& rflags, V3& w,
+                                           V3& o, vg_ray_hit& h) {
   const M3 R = ld_m3(pose.v);
   const V3 p = ld_v3(pose.v + 9);
-  const V3 o = rigid(R, ld_v3(mp.extt), p);
+  o = rigid(R, ld_v3(mp.extt), p);
   w = rigid(R, rigid(ld_m3(mp.extR), pb, ld_v3(mp.extt)), p);
   const V3 dv = sub(w, o);
   const double r = norm3(dv);
@@ -50,7 +52,6 @@ __device__ __forceinline__ void diff_point(const MP& mp, const DevMap& m, const 
   RayPrm q = prm.ray;
   const double reach = r + (prm.gate_sigma * sqrt(dept2 + beam2 * (1.0 - mc2) / mc2) + 1.0);
   if (reach < q.t_max) q.t_max = reach;
-  vg_ray_hit h;
   ray_trace(m, mp.vs, o, dv, q, h);
   rflags = h.flags;
   dp.cls = VG_DIFF_UNKNOWN;
@@ -75,6 +76,12 @@ __device__ __forceinline__ void diff_point(const MP& mp, const DevMap& m, const 
       dp.cls = diff > gate ? VG_DIFF_APPEARED : VG_DIFF_VANISHED;
     }
   }
+}
+__device__ __forceinline__ void diff_point(const MP& mp, const DevMap& m, const V3& pb, const Pose12& pose,
+                                           const DiffPrm& prm, vg_diff_point& dp, double& av, int& rflags, V3& w) {
+  V3 o;
+  vg_ray_hit h;
+  diff_point(mp, m, pb, pose, prm, dp, av, rflags, w, o, h);
 }
 
 // the wave's counts into the summary's six ints: one atomic per class that

@@ -407,6 +407,20 @@ struct RayBufs {
   int cap = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the last call's kernels (vgx_ray_ms)
 };
+// vg_localizability / vg_scan_info staging (localizability.hip), allocated on first
+// use, freed by vg_destroy (info_free)
+constexpr int kInfoSlab = 4096;     // places per launch of k_info_places
+constexpr int kInfoMaxDirs = 4096;  // D's limit
+struct InfoBufs {
+  double* pos = nullptr;   // slab x 3 origins
+  double* dirs = nullptr;  // kInfoMaxDirs x 3 directions
+  void* out = nullptr;     // slab vg_info_rec records (vg_scan_info: the first)
+  void* part = nullptr;    // vg_scan_info: one InfoPart per workgroup of max_points_per_scan points
+  int slab = 0;            // 0: not allocated
+  int slab_want = 0;       // vgx_info_slab (0: kInfoSlab)
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
+  double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_info_ms)
+};
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
 // Only integer atomics write it, one accumulate call at a time (vg_ctx::change_mu of the owner).
@@ -588,6 +602,7 @@ struct vg_ctx {
   void* fleet = nullptr;      // a fleet's tracker (vg_fleet_create): stepped only through the fleet
   vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
   vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
+  vg::InfoBufs info;         // vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -981,6 +996,13 @@ int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
 void ray_free(vg_ctx* ctx);
 int ray_bufs(vg_ctx* ctx);  // the staging, allocated on first use
 void diff_sum_launch(hipStream_t s, const double* absv, int n, vg_diff_summary* d_sum);  // k_diff_sum
+// localizability.hip: the information matrix per place / of a scan at pose12 (host arrays in, host records out;
+// synchronous on the context stream, which the caller drained)
+int localizability_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
+                       const vg_info_params* prm, vg_info_rec* out);
+int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
+                  const vg_diff_params* diff, const vg_info_params* prm, vg_info_rec* out);
+void info_free(vg_ctx* ctx);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 void change_free(ChangeLayer* L);
@@ -1008,6 +1030,11 @@ int host_raycast(vg_ctx* ctx, const double* origins, int n_origins, const double
                  const vg_ray_params* prm, vg_ray_hit* out);
 int host_scan_diff(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* prm,
                    vg_diff_point* per_point, vg_diff_summary* out);
+// localizability_host.cpp: the two calls behind the C-ABI
+int host_localizability(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
+                        const vg_info_params* prm, vg_info_rec* out);
+int host_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* diff,
+                   const vg_info_params* prm, vg_info_rec* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

@@ -14,7 +14,7 @@
 //
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
-//        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff]
+//        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
 //         [--changes FILE [--changes-scans FILE]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
@@ -32,6 +32,11 @@
 // --scan-diff (with --localize): every localised scan's downsampled cloud is checked against the map at
 // its IEKF pose (vg_scan_diff) and one line per scan goes to stdout ahead of the summary line:
 //   scan_diff <scan index> <scan end time> <n_ds> <unknown> <consistent> <appeared> <vanished>
+// --scan-info (with --localize): the expected pose information of every localised scan's downsampled cloud at
+// the pose just estimated (vg_scan_info, its CONSISTENT points), one line per scan on stdout:
+//   scan_info <scan index> <scan end time> <n_hits> <eig_t[0]> <dir_t x y z> <eig_r[0]>
+// (doubles with 9 significant digits; the smallest eigenvalue of the translation information with the rotation
+// marginalised, its direction in the world, and the rotation's).
 // --changes FILE (with --localize): a change layer is begun on the loaded map, every localised scan's
 // downsampled cloud accumulated at its IEKF pose (vg_change_accumulate; its summary feeds --scan-diff),
 // and the report of everything touched (query flags 1, default rule) written as CSV at the end, doubles
@@ -55,7 +60,7 @@ int main(int argc0, char** argv0) {
   std::vector<char*> pos;
   std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans;
   int ck_at = -1;
-  bool localize = false, scan_diff = false, global = false;
+  bool localize = false, scan_diff = false, scan_info = false, global = false;
   double places_step = 1.0;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
@@ -70,13 +75,14 @@ int main(int argc0, char** argv0) {
     else if (a == "--localize") localize = true;
     else if (a == "--global") global = true;
     else if (a == "--scan-diff") scan_diff = true;
+    else if (a == "--scan-info") scan_info = true;
     else pos.push_back(argv0[i]);
   }
   const int argc = (int)pos.size();
   char** argv = pos.data();
   const bool changes = !changes_file.empty();
-  if ((scan_diff || changes) && !localize) {
-    fprintf(stderr, "%s: --scan-diff and --changes need --map FILE --localize\n", argv0[0]);
+  if ((scan_diff || scan_info || changes) && !localize) {
+    fprintf(stderr, "%s: --scan-diff, --scan-info and --changes need --map FILE --localize\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -220,7 +226,7 @@ int main(int argc0, char** argv0) {
         return 1;
       }
     }
-    if (scan_diff || changes)
+    if (scan_diff || scan_info || changes)
       node.set_after_step([&]() {
         vg_ctx* c = node.lio().raw();
         int n = 0;
@@ -231,6 +237,15 @@ int main(int argc0, char** argv0) {
         if (n > 0 && vg_scan_points(c, ds.data(), n, &n) != VG_OK)
           throw vina_gpu::Error(VG_E_STATE, std::string("vg_scan_points: ") + vg_last_error(c));
         const double* pose = st + 1;  // R row-major, p: the pose after the scan's IEKF
+        if (scan_info) {
+          const vg_info_rec r = node.lio().scan_info(ds.data(), n, pose);
+          printf("scan_info %d %.9f %d %.9g %.9g %.9g %.9g %.9g\n", n_diffed, st[0], r.n_hits, r.eig_t[0], r.dir_t[0],
+                 r.dir_t[1], r.dir_t[2], r.eig_r[0]);
+        }
+        if (!scan_diff && !changes) {
+          n_diffed++;
+          return;
+        }
         const vg_diff_summary sm = changes ? node.lio().change_accumulate(ds.data(), n, pose)
                                            : node.lio().scan_diff(ds.data(), n, pose);
         if (fscans) {

@@ -118,6 +118,20 @@ class DiffSummary(ctypes.Structure):
                 ("sum_abs_consistent", ctypes.c_double), ("reserved", ctypes.c_double * 3)]
 
 
+class InfoParams(ctypes.Structure):
+    """vg_info_params, 112 bytes."""
+    _fields_ = [("ray", RayParams), ("floor_var", ctypes.c_double), ("min_hits", ctypes.c_int), ("pad", ctypes.c_int),
+                ("reserved", ctypes.c_double * 4)]
+
+
+class InfoRec(ctypes.Structure):
+    """vg_info_rec: one place's (one scan's) information record, 416 bytes."""
+    _fields_ = [("H", ctypes.c_double * 36), ("eig_t", ctypes.c_double * 3), ("eig_r", ctypes.c_double * 3),
+                ("dir_t", ctypes.c_double * 3), ("dir_r", ctypes.c_double * 3), ("sum_w", ctypes.c_double),
+                ("reserved", ctypes.c_double), ("n_rays", ctypes.c_int32), ("n_hits", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class ChangeParams(ctypes.Structure):
     """vg_change_params."""
     _fields_ = [("diff", DiffParams), ("cell", ctypes.c_double), ("cell_hash_log2", ctypes.c_int),
@@ -198,6 +212,13 @@ RAY_HIT, RAY_TRUNCATED, RAY_OCCUPIED, RAY_LEFT_RANGE, RAY_INVALID = 1, 2, 4, 8, 
 DIFF_UNKNOWN, DIFF_CONSISTENT, DIFF_APPEARED, DIFF_VANISHED = 0, 1, 2, 3
 
 
+INFO_REC_DTYPE = np.dtype([("H", "<f8", (6, 6)), ("eig_t", "<f8", 3), ("eig_r", "<f8", 3), ("dir_t", "<f8", 3),
+                           ("dir_r", "<f8", 3), ("sum_w", "<f8"), ("reserved", "<f8"), ("n_rays", "<i4"),
+                           ("n_hits", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
+INFO_VALID, INFO_ROT_DEGENERATE, INFO_TRANS_DEGENERATE, INFO_RAY_ENDED = 1, 2, 4, 8
+INFO_MAX_DIRS = 4096
+
+
 def ray_params(t_min=0.0, t_max=0.0, min_cos=0.0, max_steps=0):
     """vg_ray_params; zeros take the defaults (100 m, 0.05, 4096)."""
     p = RayParams()
@@ -210,6 +231,14 @@ def diff_params(gate_sigma=0.0, gate_floor=0.0, **ray):
     p = DiffParams()
     p.ray = ray_params(**ray)
     p.gate_sigma, p.gate_floor = gate_sigma, gate_floor
+    return p
+
+
+def info_params(floor_var=0.0, min_hits=0, **ray):
+    """vg_info_params; zeros take the defaults (no floor, 16 hits, ray_params' defaults)."""
+    p = InfoParams()
+    p.ray = ray_params(**ray)
+    p.floor_var, p.min_hits = floor_var, min_hits
     return p
 
 
@@ -355,6 +384,13 @@ def lib():
             L.vg_scan_diff.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(DiffParams), P,
                                        ctypes.POINTER(DiffSummary)]
             L.vgx_ray_ms.argtypes = [P, dp]
+        L.has_info = hasattr(L, "vg_localizability")  # a build older than the localisability calls (A/B runs)
+        if L.has_info:
+            L.vg_localizability.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(InfoParams), P]
+            L.vg_scan_info.argtypes = [P, fp, ctypes.c_int, dp, ctypes.POINTER(DiffParams),
+                                       ctypes.POINTER(InfoParams), P]
+            L.vgx_info_ms.argtypes = [P, dp]
+            L.vgx_info_slab.argtypes = [P, ctypes.c_int]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -700,6 +736,45 @@ class Context:
         rec = {"n": list(s.n), "n_truncated": s.n_truncated, "n_occupied_unknown": s.n_occupied_unknown,
                "sum_abs_consistent": s.sum_abs_consistent}
         return (rec, pp[: xyz.shape[0]]) if per_point else rec
+
+    # ---- localisability (vina_gpu.h "Localisability")
+    def localizability(self, positions, dirs, **prm):
+        """vg_localizability: one INFO_REC_DTYPE record per place. positions (M, 3): LiDAR origins in the
+        world; dirs (D, 3), 1 <= D <= 4096: world-frame directions shared by all places (places_dirs()
+        gives a suitable set); prm: info_params."""
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        p = info_params(**prm)
+        out = np.zeros(max(pos.shape[0], 1), dtype=INFO_REC_DTYPE)
+        self._chk(lib().vg_localizability(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0],
+                                          _d(d) if d.shape[0] else None, d.shape[0], ctypes.byref(p),
+                                          out.ctypes.data), "vg_localizability")
+        return out[: pos.shape[0]]
+
+    def scan_info(self, xyz, pose=None, floor_var=0.0, min_hits=0, **diff):
+        """vg_scan_info: the information record (an INFO_REC_DTYPE scalar) of the scan xyz (n, 3; LiDAR
+        frame) at pose (12,) [R row-major, p] (None: the context's state), over its CONSISTENT points;
+        diff: diff_params, as scan_diff takes them."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        dq = diff_params(**diff)
+        p = info_params(floor_var=floor_var, min_hits=min_hits)
+        out = np.zeros(1, dtype=INFO_REC_DTYPE)
+        self._chk(lib().vg_scan_info(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                     None if g is None else _d(g), ctypes.byref(dq), ctypes.byref(p),
+                                     out.ctypes.data), "vg_scan_info")
+        return out[0]
+
+    def info_ms(self):
+        """Device time (ms) of the last localizability call's kernels, summed over its slabs, or of the
+        last scan_info call's (HIP events on the context stream)."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_info_ms(self.h, ctypes.byref(ms)), "vgx_info_ms")
+        return ms.value
+
+    def info_slab(self, places):
+        """Test hook: the places per launch of localizability from the next call on (<= 0: the default)."""
+        self._chk(lib().vgx_info_slab(self.h, places), "vgx_info_slab")
 
     # ---- the change layer (vina_gpu.h "Change layer")
     def change_begin(self, cell=0.0, cell_hash_log2=0, **diff):
