@@ -556,6 +556,87 @@ int vg_localizability(vg_ctx* ctx, const double* positions, int M, const double*
 int vg_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* diff,
                  const vg_info_params* prm, vg_info_rec* out);
 
+/* ---- Occupancy grid: a 2-D navigation map ray-cast from the voxel map ----------
+ * M sensor origins x D shared directions are traced exactly as vg_raycast traces
+ * them and rasterised on the device into a grid of nx x ny square cells of edge
+ * res: cell (ix, iy) spans [x0 + ix res, x0 + (ix + 1) res] x [y0 + iy res, y0 +
+ * (iy + 1) res] in the world's x, y. Two int32 count planes are summed over all
+ * rays with integer atomics, n_free (the ray crossed the cell before its end)
+ * and n_occ (the ray's hit lies in the cell), and classified per cell. Reads the
+ * map only and keeps no state: every call starts from zero counts.
+ *
+ * Per ray (o, d), d the unit direction, with its vg_raycast record m. A ray with
+ * VG_RAY_TRUNCATED, VG_RAY_LEFT_RANGE or VG_RAY_INVALID marks nothing. Its end
+ * r_end is m.range where it hit, else free_on_miss where that is > 0, else the
+ * ray marks nothing.
+ *   Occupied mark. The hit is in band when z_lo <= m.range d_z <= z_hi (heights
+ *     relative to the ray's own origin, so that floor and ceiling stay out of
+ *     the grid). An in-band hit adds 1 to n_occ of the cell (floor((h_x - x0) /
+ *     res), floor((h_y - y0) / res)), h = o + m.range d.
+ *   Free marks. The free segment is the open interval of t between max(t_min,
+ *     0) and r_end on which z_lo <= t d_z <= z_hi. Every cell whose interior the
+ *     segment's (x, y) projection passes through gets n_free += 1, except the
+ *     in-band hit's own cell; a ray with d_x = d_y = 0 marks only the cell it
+ *     stands in. A ray marks a cell at most once. Marks outside the grid are
+ *     dropped.
+ *   flags bit 0: a ray whose record carries VG_RAY_OCCUPIED still marks its hit
+ *     but no free cell. It crossed a leaf that holds points but no plane.
+ * The limit of this grid: only planes are surfaces here. Clutter in a leaf
+ * without a plane is not an obstacle in the grid (the traversal does not report
+ * where along the ray that leaf was crossed); flags bit 0 at least keeps such a
+ * ray from declaring the space behind the clutter free.
+ *
+ * Per cell, in this order: occupied (VG_OCC_OCCUPIED) when n_occ >= min_occ and
+ * n_occ >= occ_ratio (n_occ + n_free), the product taken in double; else free
+ * (VG_OCC_FREE) when n_free >= min_free; else unknown (VG_OCC_UNKNOWN) — the
+ * values of nav_msgs/OccupancyGrid. */
+#define VG_OCC_UNKNOWN (-1)
+#define VG_OCC_FREE 0
+#define VG_OCC_OCCUPIED 100
+#define VG_OCC_MAX_CELLS (1 << 24)
+typedef struct vg_occ_params {
+  vg_ray_params ray;        /* as vg_raycast; zero fields: its defaults */
+  double x0, y0;            /* world x, y of the lower corner of cell (0, 0) */
+  double res;               /* cell edge, metres; > 0 */
+  int    nx, ny;            /* cells; 1 <= nx, ny and nx * ny <= 2^24 */
+  double z_lo, z_hi;        /* height band relative to each ray's origin: a point at o + t d is in the
+                               band when z_lo <= t d_z <= z_hi; z_lo < z_hi */
+  double free_on_miss;      /* a ray without a hit marks free up to this range; <= 0: marks nothing */
+  int    min_occ;           /* <= 0: 1 */
+  int    min_free;          /* <= 0: 1 */
+  double occ_ratio;         /* <= 0: off */
+  int    flags;             /* bit 0: a ray with VG_RAY_OCCUPIED marks no free cell */
+  int    pad;
+  double reserved[4];
+} vg_occ_params;
+typedef struct vg_occ_summary {   /* 128 bytes, no implicit padding */
+  int64_t n_rays, n_hits, n_hits_in_band, n_truncated, n_occupied_unknown, n_invalid;
+                                          /* M D; rays with VG_RAY_HIT; in-band hits of rays that mark; rays
+                                             with bit 1, bit 2, bit 4 */
+  int64_t free_marks, occ_marks;          /* sums of the two count planes */
+  int64_t cells_free, cells_occupied, cells_unknown;
+  int64_t reserved[5];
+} vg_occ_summary;
+/* positions: M x 3 doubles, sensor origins in the world (the positions the sensor
+ * really stood at: vg_path's rows moved by ext_t; free space is known from
+ * nowhere else). dirs: D x 3 doubles shared by all origins, 1 <= D <= 4096,
+ * normalised on the device. grid: nx ny int8, row-major, cell (ix, iy) at iy nx +
+ * ix. counts (may be NULL): 2 nx ny int32, the n_free plane, then the n_occ
+ * plane. All sums are integer atomics: grid, counts and summary do not depend on
+ * the order of the origins, on how M is walked in slabs or on the calling
+ * context, and the counts of two calls over a split of the origins add up to the
+ * counts of one. A plane's count is an int32: M D stays below 2^31. The planes
+ * and the grid are device buffers allocated on the first call and re-used; only
+ * grid, counts and summary leave the device. M == 0 gives an all-unknown grid.
+ * NULL ctx, prm, grid, out, dirs or (M > 0) positions; M < 0; D outside [1,
+ * 4096]; res not finite or <= 0; x0 or y0 not finite; nx or ny < 1 or nx ny >
+ * 2^24; z_lo < z_hi not true; flags with a bit above 0: VG_E_ARG. Legal where
+ * vg_raycast is: completes outstanding work first; mapping on or off; on an
+ * owner, an attached tracker and a fleet's tracker; unsharded contexts only
+ * (VG_E_STATE with world > 1). */
+int vg_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
+                 const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

@@ -154,6 +154,24 @@ class LioCore {
     check(vg_scan_info(ctx_, xyz, n, pose12, diff, prm, &out), "vg_scan_info");
     return out;
   }
+  // the occupancy grid (vina_gpu.h "Occupancy grid"): M origins x D shared directions rasterised on the
+  // device; grid: nx ny cells of VG_OCC_*, row-major; counts (with_counts): n_free's plane, then n_occ's
+  struct Occupancy {
+    std::vector<int8_t> grid;
+    std::vector<int32_t> counts;
+    vg_occ_summary summary;
+  };
+  Occupancy occupancy(const double* positions, int M, const double* dirs, int D, const vg_occ_params& prm,
+                      bool with_counts = false) {
+    Occupancy r;
+    const size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    r.grid.resize(cells <= (size_t)VG_OCC_MAX_CELLS ? cells : 1);
+    if (with_counts) r.counts.resize(2 * r.grid.size());
+    check(vg_occupancy(ctx_, positions, M, dirs, D, &prm, r.grid.data(), with_counts ? r.counts.data() : nullptr,
+                       &r.summary),
+          "vg_occupancy");
+    return r;
+  }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
   // owner or any tracker attached to it; prm / q null: the defaults
   void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }

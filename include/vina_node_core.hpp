@@ -82,6 +82,47 @@ struct NodeParams {
   std::string map_path;
 };
 
+// The 2-D navigation map of the node (nav_msgs/OccupancyGrid's content; vina_gpu.h "Occupancy grid")
+struct OccupancyGridParams {
+  double res = 0.1;      // cell edge, metres; the path's sensor origins are thinned to one per res
+  double margin = 20.0;  // the grid reaches this far past the origins' bounds; the rays' t_max where occ.ray.t_max is 0
+  int n_az = 360;        // the fan: n_az azimuths about the world's z at each elevation
+  std::vector<double> elevations_deg = {-10.0, 0.0, 10.0};
+  vg_occ_params occ = {};  // band (z_lo < z_hi not set: -0.3 .. 1.0), thresholds, flags, ray; the grid's fields are filled in
+};
+struct OccupancyGrid {
+  double x0 = 0, y0 = 0, res = 0;
+  int nx = 0, ny = 0;
+  std::vector<int8_t> data;  // VG_OCC_*, row-major, cell (ix, iy) at iy nx + ix
+  vg_occ_summary summary = {};
+  std::vector<double> origins, dirs;  // what was cast: M x 3, D x 3
+  vg_occ_params params = {};          // ... with these parameters
+};
+// map_server's pair: prefix.pgm (P5, the first row at the largest y; occupied 0, free 254, unknown 205) and prefix.yaml
+inline bool write_occupancy_map(const std::string& prefix, const OccupancyGrid& g) {
+  FILE* f = fopen((prefix + ".pgm").c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "P5\n%d %d\n255\n", g.nx, g.ny);
+  std::vector<unsigned char> row((size_t)g.nx);
+  for (int iy = g.ny - 1; iy >= 0; iy--) {
+    for (int ix = 0; ix < g.nx; ix++) {
+      const int8_t c = g.data[(size_t)iy * g.nx + ix];
+      row[ix] = c == VG_OCC_OCCUPIED ? 0 : (c == VG_OCC_FREE ? 254 : 205);
+    }
+    if (fwrite(row.data(), 1, row.size(), f) != row.size()) {
+      fclose(f);
+      return false;
+    }
+  }
+  if (fclose(f) != 0) return false;
+  const size_t slash = prefix.find_last_of('/');
+  f = fopen((prefix + ".yaml").c_str(), "w");
+  if (!f) return false;
+  fprintf(f, "image: %s.pgm\nresolution: %.17g\norigin: [%.17g, %.17g, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n",
+          prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), g.res, g.x0, g.y0);
+  return fclose(f) == 0;
+}
+
 class NodeCore {
  public:
   // cfg.cold_start = 1 for a run from a bag (the node's initialization,
@@ -317,6 +358,52 @@ class NodeCore {
         out[3 * i + r] = (float)(s.R[3 * r] * b[0] + s.R[3 * r + 1] * b[1] + s.R[3 * r + 2] * b[2] + s.p[r]);
     }
     return out;
+  }
+
+  // The occupancy grid cast from the node's own path (vg_occupancy): the sensor origins p + R ext_t of
+  // path()'s rows — a loaded map's rows included, the only places from which free space is known —
+  // thinned so that every kept origin is at least res from the one kept before it, on the grid that
+  // covers their x, y bounds grown by margin (x0, y0 whole multiples of res). Completes outstanding work.
+  OccupancyGrid occupancy_grid(const OccupancyGridParams& P = OccupancyGridParams()) {
+    finish();
+    OccupancyGrid g;
+    if (!(P.res > 0.0) || !(P.margin >= 0.0) || P.n_az < 1 || P.elevations_deg.empty())
+      throw Error(VG_E_ARG, "occupancy_grid: res, margin, n_az or the elevations");
+    double lo[2] = {0, 0}, hi[2] = {0, 0};
+    for (const PoseStamped& s : path_) {
+      double o[3];
+      for (int j = 0; j < 3; j++)
+        o[j] = s.p[j] + s.R[3 * j] * cfg_.ext_t[0] + s.R[3 * j + 1] * cfg_.ext_t[1] + s.R[3 * j + 2] * cfg_.ext_t[2];
+      const size_t m = g.origins.size();
+      if (m && std::hypot(std::hypot(o[0] - g.origins[m - 3], o[1] - g.origins[m - 2]), o[2] - g.origins[m - 1]) < P.res)
+        continue;
+      for (int j = 0; j < 2; j++) {
+        lo[j] = m && lo[j] < o[j] ? lo[j] : o[j];
+        hi[j] = m && hi[j] > o[j] ? hi[j] : o[j];
+      }
+      g.origins.insert(g.origins.end(), o, o + 3);
+    }
+    if (g.origins.empty()) throw Error(VG_E_STATE, "occupancy_grid: the path is empty");
+    for (const double e : P.elevations_deg)
+      for (int a = 0; a < P.n_az; a++) {
+        const double az = 2.0 * M_PI * a / P.n_az, el = e * M_PI / 180.0;
+        const double d[3] = {std::cos(el) * std::cos(az), std::cos(el) * std::sin(az), std::sin(el)};
+        g.dirs.insert(g.dirs.end(), d, d + 3);
+      }
+    vg_occ_params q = P.occ;
+    if (!(q.z_lo < q.z_hi)) q.z_lo = -0.3, q.z_hi = 1.0;
+    if (!(q.ray.t_max > 0.0) && P.margin > 0.0) q.ray.t_max = P.margin;
+    const double kx = std::floor((lo[0] - P.margin) / P.res), ky = std::floor((lo[1] - P.margin) / P.res);
+    const double nx = std::ceil((hi[0] + P.margin) / P.res) - kx, ny = std::ceil((hi[1] + P.margin) / P.res) - ky;
+    if (!(nx * ny <= (double)VG_OCC_MAX_CELLS)) throw Error(VG_E_ARG, "occupancy_grid: more than 2^24 cells");
+    q.x0 = g.x0 = kx * P.res, q.y0 = g.y0 = ky * P.res, q.res = g.res = P.res;
+    q.nx = g.nx = nx < 1.0 ? 1 : (int)nx, q.ny = g.ny = ny < 1.0 ? 1 : (int)ny;
+    LioCore::Occupancy r = lio_.occupancy(g.origins.data(), (int)(g.origins.size() / 3), g.dirs.data(),
+                                          (int)(g.dirs.size() / 3), q);
+    g.data = std::move(r.grid);
+    g.summary = r.summary;
+    g.params = q;
+    return g;
   }
 
   bool write_tum(const std::string& file) {

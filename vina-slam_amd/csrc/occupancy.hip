@@ -1,0 +1,179 @@
+// occupancy.hip — the 2-D occupancy grid ray-cast from the voxel map
+// (vg_occupancy; vina_gpu.h "Occupancy grid"): M origins x D shared directions
+// traced through vg_ray.h and rasterised on the device (vg_occ.h), so that only
+// the grid, the optional count planes and a 128-byte summary leave it.
+//
+// k_occ_cast: one lane per (place, direction), lane i = place D + direction,
+// 256-thread workgroups, no LDS. ray_trace is the latency-bound gather it is in
+// k_raycast; the walk behind it is arithmetic in registers and one int32
+// atomicAdd per marked cell. The lanes of a wave share an origin (D >= 64), so
+// their first cells coincide and the cell under the sensor takes D atomics per
+// place; they are not merged within the wave (DESIGN.md §6 has the measurement).
+// The summary's ray counts: one 64-bit atomic per wave and count that occurs.
+//
+// k_occ_classify: one lane per cell; writes the grid and adds the wave's class
+// counts and the two planes' sums to the summary, one atomic per wave each.
+//
+// Every sum is an integer atomic: the planes, the grid and the summary do not
+// depend on the order of the rays or on how M is cut into launches.
+#include "vg_occ.h"
+
+namespace vg {
+
+// the summary's int64 slots as the kernels index them (vg_occ_summary's order)
+enum { kOccRays = 0, kOccHits, kOccInBand, kOccTrunc, kOccOccupied, kOccInvalid, kOccFreeMarks, kOccOccMarks,
+       kOccCellsFree, kOccCellsOccupied, kOccCellsUnknown };
+
+__device__ __forceinline__ void occ_wave_add(unsigned long long* __restrict__ sum, int slot, bool mine) {
+  const unsigned long long b = __ballot(mine);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&sum[slot], (unsigned long long)__popcll(b));
+}
+
+__global__ void __launch_bounds__(kOccBlock) k_occ_cast(double vs, DevMap m, const double* __restrict__ pos,
+                                                        const double* __restrict__ dirs, int D, int n, OccPrm prm,
+                                                        int* __restrict__ n_free, int* __restrict__ n_occ,
+                                                        unsigned long long* __restrict__ sum) {
+  const int i = blockIdx.x * kOccBlock + threadIdx.x;
+  const bool valid = i < n;
+  int flags = 0;
+  bool in_band = false;
+  if (valid) {
+    const int place = i / D, k = i - place * D;
+    const V3 o = ld_v3(pos + 3 * (size_t)place), dir = ld_v3(dirs + 3 * (size_t)k);
+    vg_ray_hit h;
+    ray_trace(m, vs, o, dir, prm.ray, h);
+    flags = h.flags;
+    occ_ray(prm, o, dir, h, n_free, n_occ, in_band);
+  }
+  occ_wave_add(sum, kOccHits, valid && (flags & kRayHit));
+  occ_wave_add(sum, kOccInBand, in_band);
+  occ_wave_add(sum, kOccTrunc, valid && (flags & kRayTruncated));
+  occ_wave_add(sum, kOccOccupied, valid && (flags & kRayOccupied));
+  occ_wave_add(sum, kOccInvalid, valid && (flags & kRayInvalid));
+}
+
+__global__ void __launch_bounds__(kOccBlock) k_occ_classify(const int* __restrict__ n_free,
+                                                            const int* __restrict__ n_occ, int cells, int min_occ,
+                                                            int min_free, double occ_ratio,
+                                                            int8_t* __restrict__ grid,
+                                                            unsigned long long* __restrict__ sum) {
+  const int i = blockIdx.x * kOccBlock + threadIdx.x;
+  int f = 0, o = 0, cls = 1;  // cls: the lanes past the last cell count nowhere
+  if (i < cells) {
+    f = n_free[i];
+    o = n_occ[i];
+    if (o >= min_occ && (double)o >= occ_ratio * ((double)o + (double)f)) cls = VG_OCC_OCCUPIED;
+    else cls = f >= min_free ? VG_OCC_FREE : VG_OCC_UNKNOWN;
+    grid[i] = (int8_t)cls;
+  }
+  occ_wave_add(sum, kOccCellsFree, cls == VG_OCC_FREE);
+  occ_wave_add(sum, kOccCellsOccupied, cls == VG_OCC_OCCUPIED);
+  occ_wave_add(sum, kOccCellsUnknown, cls == VG_OCC_UNKNOWN);
+  // the planes' sums, in 64 bits: 64 counts of up to M D each
+  unsigned long long sf = (unsigned long long)f, so = (unsigned long long)o;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sf += __shfl_down(sf, off, 64);
+    so += __shfl_down(so, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (sf) atomicAdd(&sum[kOccFreeMarks], sf);
+    if (so) atomicAdd(&sum[kOccOccMarks], so);
+  }
+}
+
+// ---- host side
+
+static int occ_bufs(vg_ctx* ctx, size_t cells) {
+  OccBufs& b = ctx->occ;
+  static_assert(sizeof(vg_occ_params) == 176 && sizeof(vg_occ_summary) == 128, "the records' documented sizes");
+  if (!b.ready) {
+    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.pos), (size_t)kInfoSlab * 3 * sizeof(double)));
+    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dirs), (size_t)kInfoMaxDirs * 3 * sizeof(double)));
+    VG_HIP(hipMalloc(&b.sum, sizeof(vg_occ_summary)));
+    for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
+    b.ready = true;
+  }
+  if (cells > b.cells) {
+    if (b.planes) (void)hipFree(b.planes);
+    if (b.grid) (void)hipFree(b.grid);
+    b.planes = nullptr;
+    b.grid = nullptr;
+    b.cells = 0;
+    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.planes), 2 * cells * sizeof(int)));
+    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.grid), cells));
+    b.cells = cells;
+  }
+  return VG_OK;
+}
+
+void occ_free(vg_ctx* ctx) {
+  OccBufs& b = ctx->occ;
+  if (b.pos) (void)hipFree(b.pos);
+  if (b.dirs) (void)hipFree(b.dirs);
+  if (b.planes) (void)hipFree(b.planes);
+  if (b.grid) (void)hipFree(b.grid);
+  if (b.sum) (void)hipFree(b.sum);
+  for (auto& e : b.ev)
+    if (e) (void)hipEventDestroy(e);
+  b = OccBufs();
+}
+
+static int occ_elapsed(vg_ctx* ctx) {
+  OccBufs& b = ctx->occ;
+  float t = 0;
+  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
+  b.ms += t;
+  return VG_OK;
+}
+
+int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
+                  const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out) {
+  const size_t cells = (size_t)prm->nx * (size_t)prm->ny;
+  VG_TRY(occ_bufs(ctx, cells));
+  OccBufs& b = ctx->occ;
+  hipStream_t s = ctx->stream;
+  const OccPrm q = occ_prm(prm);
+  unsigned long long* d_sum = static_cast<unsigned long long*>(b.sum);
+  int* d_free = b.planes;
+  int* d_occ = b.planes + cells;
+  const int slab = kInfoSlab;  // (slab D <= 2^24 lanes per launch)
+  b.ms = 0.0;
+  VG_HIP(hipMemsetAsync(b.planes, 0, 2 * cells * sizeof(int), s));
+  VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_occ_summary), s));
+  if (M > 0) VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  for (int i0 = 0; i0 < M; i0 += slab) {
+    const int m = M - i0 < slab ? M - i0 : slab;
+    const int n = m * D;
+    VG_HIP(hipMemcpyAsync(b.pos, positions + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    VG_HIP(hipEventRecord(b.ev[0], s));
+    k_occ_cast<<<(n + kOccBlock - 1) / kOccBlock, kOccBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, n, q, d_free,
+                                                                     d_occ, d_sum);
+    VG_HIP(hipEventRecord(b.ev[1], s));
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
+    VG_TRY(occ_elapsed(ctx));
+  }
+  VG_HIP(hipEventRecord(b.ev[0], s));
+  k_occ_classify<<<(int)((cells + kOccBlock - 1) / kOccBlock), kOccBlock, 0, s>>>(d_free, d_occ, (int)cells, q.min_occ,
+                                                                                  q.min_free, q.occ_ratio, b.grid, d_sum);
+  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(hipGetLastError());
+  VG_HIP(hipMemcpyAsync(grid, b.grid, cells, hipMemcpyDeviceToHost, s));
+  if (counts) VG_HIP(hipMemcpyAsync(counts, b.planes, 2 * cells * sizeof(int), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_occ_summary), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipStreamSynchronize(s));
+  VG_TRY(occ_elapsed(ctx));
+  out->n_rays = (int64_t)M * (int64_t)D;
+  return VG_OK;
+}
+
+}  // namespace vg
+
+// Measurement hook: the device time of the last vg_occupancy call's kernels, summed over its slabs and the
+// classification (HIP events on the context stream around them)
+extern "C" int vgx_occ_ms(vg_ctx* ctx, double* ms) {
+  if (!ctx || !ms || !ctx->occ.ev[0]) return VG_E_ARG;
+  *ms = ctx->occ.ms;
+  return VG_OK;
+}

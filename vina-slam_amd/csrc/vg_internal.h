@@ -421,6 +421,19 @@ struct InfoBufs {
   hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
   double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_info_ms)
 };
+// vg_occupancy staging (occupancy.hip), allocated on first use and grown to the
+// largest grid asked for, freed by vg_destroy (occ_free)
+struct OccBufs {
+  double* pos = nullptr;   // kInfoSlab x 3 origins
+  double* dirs = nullptr;  // kInfoMaxDirs x 3 directions
+  int* planes = nullptr;   // 2 x cells: n_free, then n_occ
+  int8_t* grid = nullptr;  // cells
+  void* sum = nullptr;     // one vg_occ_summary
+  size_t cells = 0;        // capacity of planes / grid, in cells
+  bool ready = false;      // pos, dirs, sum and the events exist
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
+  double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_occ_ms)
+};
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
 // Only integer atomics write it, one accumulate call at a time (vg_ctx::change_mu of the owner).
@@ -603,6 +616,7 @@ struct vg_ctx {
   vg::ScoreBufs score;       // vg_score_poses / vg_relocalize scratch (score.hip), allocated on first use
   vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
   vg::InfoBufs info;         // vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
+  vg::OccBufs occ;           // vg_occupancy staging and count planes (occupancy.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -1003,6 +1017,11 @@ int localizability_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M
 int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
                   const vg_diff_params* diff, const vg_info_params* prm, vg_info_rec* out);
 void info_free(vg_ctx* ctx);
+// occupancy.hip: the occupancy grid of M origins x D directions (host arrays in; grid, counts (or null) and
+// summary out; synchronous on the context stream, which the caller drained). prm: checked by the caller
+int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
+                  const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
+void occ_free(vg_ctx* ctx);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 void change_free(ChangeLayer* L);
@@ -1035,6 +1054,9 @@ int host_localizability(vg_ctx* ctx, const double* positions, int M, const doubl
                         const vg_info_params* prm, vg_info_rec* out);
 int host_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* diff,
                    const vg_info_params* prm, vg_info_rec* out);
+// occupancy_host.cpp: the call behind the C-ABI
+int host_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D, const vg_occ_params* prm,
+                   int8_t* grid, int32_t* counts, vg_occ_summary* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

@@ -15,7 +15,7 @@
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
-//         [--changes FILE [--changes-scans FILE]]]
+//         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
@@ -46,6 +46,13 @@
 //   totals,calls,points,unknown,consistent,appeared,vanished,cells_used,dropped,out_of_range,leaves_touched
 // (flags bit 0: the leaf meets the removed rule / the cell the added rule). --changes-scans FILE: what was
 // accumulated, per scan int32 n, double pose[12], float xyz[3 n], to check the report against the API.
+// --occupancy PREFIX (with --localize): at the end of the run the 2-D occupancy grid is cast from the node's
+// path — the loaded map's rows and the localised scans' — (NodeCore::occupancy_grid: vg_occupancy on the
+// sensor origins thinned to one per cell edge; --occ-res R metres, default 0.1) and written in map_server's
+// form: PREFIX.pgm (P5, the first row at the largest y; occupied 0, free 254, unknown 205) and PREFIX.yaml
+// (image, resolution, origin: [x0, y0, 0], negate: 0, occupied_thresh: 0.65, free_thresh: 0.196). Leaves
+// without a plane are not obstacles in this grid. --occ-rays FILE: what was cast, int32 M, int32 D, the
+// vg_occ_params used, double origins[3 M], double dirs[3 D], to check the grid against the API.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -58,7 +65,8 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
-  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans;
+  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays;
+  double occ_res = 0.1;
   int ck_at = -1;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
   double places_step = 1.0;
@@ -72,6 +80,9 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--changes") changes_file = argv0[++i];
     else if (i + 1 < argc0 && a == "--changes-scans") changes_scans = argv0[++i];
     else if (i + 1 < argc0 && a == "--places-step") places_step = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--occupancy") occ_prefix = argv0[++i];
+    else if (i + 1 < argc0 && a == "--occ-res") occ_res = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--occ-rays") occ_rays = argv0[++i];
     else if (a == "--localize") localize = true;
     else if (a == "--global") global = true;
     else if (a == "--scan-diff") scan_diff = true;
@@ -81,8 +92,12 @@ int main(int argc0, char** argv0) {
   const int argc = (int)pos.size();
   char** argv = pos.data();
   const bool changes = !changes_file.empty();
-  if ((scan_diff || scan_info || changes) && !localize) {
-    fprintf(stderr, "%s: --scan-diff, --scan-info and --changes need --map FILE --localize\n", argv0[0]);
+  if ((scan_diff || scan_info || changes || !occ_prefix.empty()) && !localize) {
+    fprintf(stderr, "%s: --scan-diff, --scan-info, --changes and --occupancy need --map FILE --localize\n", argv0[0]);
+    return 2;
+  }
+  if ((!occ_rays.empty() && occ_prefix.empty()) || !(occ_res > 0.0)) {
+    fprintf(stderr, "%s: --occ-rays needs --occupancy PREFIX, --occ-res a positive edge\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -348,6 +363,29 @@ int main(int argc0, char** argv0) {
       if (fclose(fc) != 0) {
         perror("changes");
         return 1;
+      }
+    }
+    if (!occ_prefix.empty()) {
+      vina_gpu::OccupancyGridParams op;
+      op.res = occ_res;
+      const vina_gpu::OccupancyGrid og = node.occupancy_grid(op);
+      if (!vina_gpu::write_occupancy_map(occ_prefix, og)) {
+        perror("occupancy");
+        return 1;
+      }
+      const vg_occ_summary& sm = og.summary;
+      fprintf(stderr, "occupancy: %d x %d cells of %g m from %d origins x %d directions: %lld occupied, %lld free, %lld unknown\n",
+              og.nx, og.ny, og.res, (int)(og.origins.size() / 3), (int)(og.dirs.size() / 3), (long long)sm.cells_occupied,
+              (long long)sm.cells_free, (long long)sm.cells_unknown);
+      if (!occ_rays.empty()) {
+        const int32_t md[2] = {(int32_t)(og.origins.size() / 3), (int32_t)(og.dirs.size() / 3)};
+        FILE* fr = fopen(occ_rays.c_str(), "wb");
+        if (!fr || fwrite(md, sizeof(md), 1, fr) != 1 || fwrite(&og.params, sizeof(og.params), 1, fr) != 1 ||
+            fwrite(og.origins.data(), sizeof(double), og.origins.size(), fr) != og.origins.size() ||
+            fwrite(og.dirs.data(), sizeof(double), og.dirs.size(), fr) != og.dirs.size() || fclose(fr) != 0) {
+          perror("occ-rays");
+          return 1;
+        }
       }
     }
     const std::vector<float> w = node.scan_world();

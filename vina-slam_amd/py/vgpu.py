@@ -132,6 +132,93 @@ class InfoRec(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class OccParams(ctypes.Structure):
+    """vg_occ_params, 176 bytes."""
+    _fields_ = [("ray", RayParams), ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("res", ctypes.c_double),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("z_lo", ctypes.c_double), ("z_hi", ctypes.c_double),
+                ("free_on_miss", ctypes.c_double), ("min_occ", ctypes.c_int), ("min_free", ctypes.c_int),
+                ("occ_ratio", ctypes.c_double), ("flags", ctypes.c_int), ("pad", ctypes.c_int),
+                ("reserved", ctypes.c_double * 4)]
+
+
+class OccSummary(ctypes.Structure):
+    """vg_occ_summary, 128 bytes."""
+    _fields_ = [("n_rays", ctypes.c_int64), ("n_hits", ctypes.c_int64), ("n_hits_in_band", ctypes.c_int64),
+                ("n_truncated", ctypes.c_int64), ("n_occupied_unknown", ctypes.c_int64), ("n_invalid", ctypes.c_int64),
+                ("free_marks", ctypes.c_int64), ("occ_marks", ctypes.c_int64), ("cells_free", ctypes.c_int64),
+                ("cells_occupied", ctypes.c_int64), ("cells_unknown", ctypes.c_int64), ("reserved", ctypes.c_int64 * 5)]
+
+
+OCC_UNKNOWN, OCC_FREE, OCC_OCCUPIED = -1, 0, 100
+OCC_MAX_CELLS = 1 << 24
+OCC_PGM = {OCC_OCCUPIED: 0, OCC_FREE: 254, OCC_UNKNOWN: 205}   # map_server's grey levels
+
+
+def occ_params(x0=0.0, y0=0.0, res=0.0, nx=0, ny=0, z_lo=-0.3, z_hi=1.0, free_on_miss=0.0, min_occ=0, min_free=0,
+               occ_ratio=0.0, flags=0, **ray):
+    """vg_occ_params; the band defaults to 0.3 m below .. 1 m above the sensor, zeros elsewhere take the
+    library's defaults (one mark classifies a cell, no ratio test, a miss marks nothing)."""
+    p = OccParams()
+    p.ray = ray_params(**ray)
+    p.x0, p.y0, p.res, p.nx, p.ny = x0, y0, res, nx, ny
+    p.z_lo, p.z_hi, p.free_on_miss = z_lo, z_hi, free_on_miss
+    p.min_occ, p.min_free, p.occ_ratio, p.flags = min_occ, min_free, occ_ratio, flags
+    return p
+
+
+def occupancy_dirs(n_az=360, elevations_deg=(-10, 0, 10)):
+    """(len(elevations_deg) * n_az, 3) unit directions, entry e * n_az + a: azimuth 2 pi a / n_az about the
+    world's z at each elevation: the horizontal-biased fan Context.occupancy casts by default (no device)."""
+    az = 2.0 * np.pi * np.arange(int(n_az)) / int(n_az)
+    el = np.deg2rad(np.asarray(elevations_deg, dtype=np.float64).reshape(-1))
+    E, A = np.meshgrid(el, az, indexing="ij")
+    return np.stack([np.cos(E) * np.cos(A), np.cos(E) * np.sin(A), np.sin(E)], -1).reshape(-1, 3)
+
+
+def grid_around(positions, res, margin):
+    """(x0, y0, nx, ny) of the grid of cell edge res that covers the positions' x, y bounds grown by margin
+    on every side; x0 and y0 are whole multiples of res."""
+    p = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    if p.shape[0] == 0:
+        raise ValueError("grid_around: no positions")
+    lo, hi = p[:, :2].min(axis=0) - margin, p[:, :2].max(axis=0) + margin
+    k0 = np.floor(lo / res)
+    n = np.maximum(np.ceil(hi / res) - k0, 1.0)
+    return float(k0[0] * res), float(k0[1] * res), int(n[0]), int(n[1])
+
+
+def write_occupancy(prefix, grid, x0, y0, res):
+    """The grid (int8 [ny, nx], OCC_*) as map_server's pair: prefix.pgm (P5, the first row at the largest y,
+    occupied 0 / free 254 / unknown 205) and prefix.yaml."""
+    g = np.asarray(grid, dtype=np.int8)
+    px = np.full(g.shape, OCC_PGM[OCC_UNKNOWN], dtype=np.uint8)
+    px[g == OCC_FREE] = OCC_PGM[OCC_FREE]
+    px[g == OCC_OCCUPIED] = OCC_PGM[OCC_OCCUPIED]
+    with open(prefix + ".pgm", "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (g.shape[1], g.shape[0]))
+        f.write(np.ascontiguousarray(px[::-1]).tobytes())
+    with open(prefix + ".yaml", "w") as f:
+        f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
+                % (os.path.basename(prefix) + ".pgm", float(res), float(x0), float(y0)))
+
+
+def read_occupancy(prefix):
+    """(grid int8 [ny, nx], x0, y0, res) back from write_occupancy's (or vg_node_replay --occupancy's) pair."""
+    meta = {}
+    for ln in open(prefix + ".yaml"):
+        k, _, v = ln.partition(":")
+        meta[k.strip()] = v.strip()
+    org = [float(x) for x in meta["origin"].strip("[]").split(",")]
+    raw = open(os.path.join(os.path.dirname(prefix), meta["image"]), "rb").read()
+    m = re.match(rb"P5\s+(\d+)\s+(\d+)\s+255\s", raw)
+    nx, ny = int(m.group(1)), int(m.group(2))
+    px = np.frombuffer(raw, dtype=np.uint8, offset=m.end(), count=nx * ny).reshape(ny, nx)[::-1]
+    g = np.full((ny, nx), OCC_UNKNOWN, dtype=np.int8)
+    g[px == OCC_PGM[OCC_FREE]] = OCC_FREE
+    g[px == OCC_PGM[OCC_OCCUPIED]] = OCC_OCCUPIED
+    return g, org[0], org[1], float(meta["resolution"])
+
+
 class ChangeParams(ctypes.Structure):
     """vg_change_params."""
     _fields_ = [("diff", DiffParams), ("cell", ctypes.c_double), ("cell_hash_log2", ctypes.c_int),
@@ -391,6 +478,11 @@ def lib():
                                        ctypes.POINTER(InfoParams), P]
             L.vgx_info_ms.argtypes = [P, dp]
             L.vgx_info_slab.argtypes = [P, ctypes.c_int]
+        L.has_occupancy = hasattr(L, "vg_occupancy")  # a build older than the occupancy grid (A/B runs)
+        if L.has_occupancy:
+            L.vg_occupancy.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(OccParams), P, P,
+                                       ctypes.POINTER(OccSummary)]
+            L.vgx_occ_ms.argtypes = [P, dp]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -775,6 +867,33 @@ class Context:
     def info_slab(self, places):
         """Test hook: the places per launch of localizability from the next call on (<= 0: the default)."""
         self._chk(lib().vgx_info_slab(self.h, places), "vgx_info_slab")
+
+    # ---- the occupancy grid (vina_gpu.h "Occupancy grid")
+    def occupancy(self, positions, dirs=None, counts=False, **params):
+        """vg_occupancy: the 2-D occupancy grid ray-cast from positions (M, 3), the sensor origins in the
+        world, along dirs (D, 3) shared by all of them (None: occupancy_dirs()). params: occ_params (x0, y0,
+        res, nx, ny and the rest) or prm=a filled OccParams. Returns (grid int8 [ny, nx] of OCC_*, counts int32 [2, ny, nx] (n_free,
+        n_occ) or None, the summary as a dict)."""
+        if not lib().has_occupancy:
+            raise VgError("this libvina_gpu.so has no occupancy grid (vg_occupancy): rebuild it")
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(occupancy_dirs() if dirs is None else dirs, dtype=np.float64).reshape(-1, 3)
+        p = params["prm"] if "prm" in params else occ_params(**params)   # prm: a filled OccParams
+        cells = p.nx * p.ny if 1 <= p.nx and 1 <= p.ny and p.nx * p.ny <= OCC_MAX_CELLS else 1
+        grid = np.zeros(cells, dtype=np.int8)
+        cnt = np.zeros(2 * cells, dtype=np.int32) if counts else None
+        s = OccSummary()
+        self._chk(lib().vg_occupancy(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0],
+                                     _d(d) if d.shape[0] else None, d.shape[0], ctypes.byref(p), grid.ctypes.data,
+                                     None if cnt is None else cnt.ctypes.data, ctypes.byref(s)), "vg_occupancy")
+        summ = {f: int(getattr(s, f)) for f, _ in OccSummary._fields_ if f != "reserved"}
+        return grid.reshape(p.ny, p.nx), None if cnt is None else cnt.reshape(2, p.ny, p.nx), summ
+
+    def occ_ms(self):
+        """Device time (ms) of the last occupancy call's kernels, summed over its slabs and the classification."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_occ_ms(self.h, ctypes.byref(ms)), "vgx_occ_ms")
+        return ms.value
 
     # ---- the change layer (vina_gpu.h "Change layer")
     def change_begin(self, cell=0.0, cell_hash_log2=0, **diff):
