@@ -637,6 +637,76 @@ typedef struct vg_occ_summary {   /* 128 bytes, no implicit padding */
 int vg_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
                  const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
 
+/* ---- Clearance field and costmap: what a planner needs of the 2-D grid ---------
+ * The exact Euclidean distance transform of an nx x ny grid of VG_OCC_* cells,
+ * its feature transform, and nav2's inflation-layer cost of the distance, all on
+ * the device. Cells are indexed i = iy nx + ix as in vg_occupancy. Reads no map
+ * and keeps no state; everything is integer arithmetic or a table look-up, so the
+ * same inputs give the same bytes from any context.
+ *
+ * The obstacle set O: the cells with value VG_OCC_OCCUPIED, and with flags bit 0
+ * those with value VG_OCC_UNKNOWN too. Any other byte value is free.
+ *   dist2[i]   = min over o in O of (ix - ox)^2 + (iy - oy)^2, an exact int32 in
+ *                cells squared: 0 on an obstacle, VG_CLR_NONE when O is empty.
+ *   nearest[i] = the linear index of the obstacle attaining that minimum, among
+ *                equals the smallest linear index; -1 when O is empty.
+ *   cost[i], with d = res sqrt((double)dist2[i]):
+ *                VG_COST_LETHAL (254) if dist2 == 0;
+ *                else VG_COST_INSCRIBED (253) if d <= inscribed_radius;
+ *                else (uint8_t)(252.0 exp(-cost_scaling (d - inscribed_radius)))
+ *                  if d <= inflation_radius;
+ *                else VG_COST_FREE (0) — also where O is empty.
+ *              An unknown cell that is not an obstacle (bit 0 clear) gets
+ *              VG_COST_NO_INFO (255) unless the value above is at least 253; then
+ *              it keeps that value (nav2's rule with inflate_unknown off).
+ * The cost formula is evaluated on the host in double, into a table indexed by
+ * dist2 with entries 0 .. floor((inflation_radius / res)^2) that the device looks
+ * up; the device's exp never enters, and the cost is a pure function of dist2.
+ *
+ * Two passes. Per column, a down and an up sweep leave every cell the signed row
+ * offset to the nearest obstacle of its own column (equal distances: the smaller
+ * iy). Per row, every cell searches outward over the columns ix -+ k for the
+ * lexicographic minimum of (k^2 + g^2, index), g the column's offset, and stops
+ * once k^2 exceeds the best so far, which is exact. */
+#define VG_CLR_NONE      INT32_MAX   /* dist2 where the grid holds no obstacle at all */
+#define VG_CLR_MAX_SIDE  32768       /* nx, ny <= this: 2 * 32767^2 < 2^31 */
+#define VG_COST_FREE 0
+#define VG_COST_INSCRIBED 253
+#define VG_COST_LETHAL 254
+#define VG_COST_NO_INFO 255
+typedef struct vg_clr_params {
+  int    nx, ny;             /* as vg_occ_params; nx ny <= VG_OCC_MAX_CELLS, each <= VG_CLR_MAX_SIDE */
+  double res;                /* cell edge, metres; finite, > 0 */
+  int    flags;              /* bit 0: an unknown cell (-1) is an obstacle too */
+  int    pad;
+  double inscribed_radius;   /* metres, >= 0 */
+  double inflation_radius;   /* metres, >= inscribed_radius */
+  double cost_scaling;       /* 1/m, >= 0 (nav2's cost_scaling_factor) */
+  double reserved[4];
+} vg_clr_params;
+typedef struct vg_clr_summary {   /* 128 bytes, no implicit padding */
+  int64_t n_obstacles, n_unknown;         /* cells in O; cells with value VG_OCC_UNKNOWN (in O or not) */
+  int64_t cells_lethal, cells_inscribed, cells_inflated, cells_free, cells_no_info;
+                                          /* cells by cost: 254, 253, 1 .. 252, 0, 255; they sum to nx ny */
+  int64_t max_dist2;                      /* the largest dist2 of any cell; 0 when O is empty */
+  int64_t reserved[8];
+} vg_clr_summary;
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call
+ * on this context left on the device, of which nothing is uploaded (VG_E_STATE
+ * when there was no such call or its nx, ny differ from prm's). dist2, nearest
+ * (nx ny int32 each) and cost (nx ny uint8) may each be NULL: that output is not
+ * copied out. The planes are device buffers allocated on first use and re-used;
+ * only the outputs asked for and the summary leave the device. NULL ctx, prm or
+ * out; nx or ny < 1 or > VG_CLR_MAX_SIDE, or nx ny > VG_OCC_MAX_CELLS; res not
+ * finite or <= 0; a radius or cost_scaling negative or not finite;
+ * inflation_radius < inscribed_radius; flags with a bit above 0; a cost table of
+ * more than 2^24 entries: VG_E_ARG, and nothing is written. Legal where
+ * vg_occupancy is: completes outstanding work first; mapping on or off; on an
+ * owner, an attached tracker and a fleet's tracker; unsharded contexts only
+ * (VG_E_STATE with world > 1). */
+int vg_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm,
+                 int32_t* dist2, int32_t* nearest, uint8_t* cost, vg_clr_summary* out);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

@@ -172,6 +172,27 @@ class LioCore {
           "vg_occupancy");
     return r;
   }
+  // the clearance field and costmap (vina_gpu.h "Clearance field and costmap") of grid (nx ny cells of
+  // VG_OCC_*; null: the grid the last occupancy() call left on the device); each output is filled only
+  // where asked for
+  struct Clearance {
+    std::vector<int32_t> dist2, nearest;
+    std::vector<uint8_t> cost;
+    vg_clr_summary summary;
+  };
+  Clearance clearance(const int8_t* grid, const vg_clr_params& prm, bool want_dist2 = true, bool want_nearest = true,
+                      bool want_cost = true) {
+    Clearance r;
+    size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    if (cells > (size_t)VG_OCC_MAX_CELLS) cells = 1;
+    if (want_dist2) r.dist2.resize(cells);
+    if (want_nearest) r.nearest.resize(cells);
+    if (want_cost) r.cost.resize(cells);
+    check(vg_clearance(ctx_, grid, &prm, want_dist2 ? r.dist2.data() : nullptr, want_nearest ? r.nearest.data() : nullptr,
+                       want_cost ? r.cost.data() : nullptr, &r.summary),
+          "vg_clearance");
+    return r;
+  }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
   // owner or any tracker attached to it; prm / q null: the defaults
   void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }

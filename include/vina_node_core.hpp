@@ -122,6 +122,35 @@ inline bool write_occupancy_map(const std::string& prefix, const OccupancyGrid& 
           prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), g.res, g.x0, g.y0);
   return fclose(f) == 0;
 }
+// The costmap of an OccupancyGrid (nav2's inflation layer; vina_gpu.h "Clearance field and costmap"), with the
+// grid's geometry
+struct Costmap {
+  double x0 = 0, y0 = 0, res = 0;
+  int nx = 0, ny = 0;
+  std::vector<uint8_t> cost;   // VG_COST_*, row-major, cell (ix, iy) at iy nx + ix
+  std::vector<int32_t> dist2;  // cells squared to the nearest obstacle; VG_CLR_NONE without any
+  vg_clr_summary summary = {};
+  vg_clr_params params = {};
+};
+// the cost's raw bytes as prefix.pgm (P5, the first row at the largest y, as write_occupancy_map flips it) and
+// write_occupancy_map's prefix.yaml
+inline bool write_costmap(const std::string& prefix, const Costmap& c) {
+  FILE* f = fopen((prefix + ".pgm").c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "P5\n%d %d\n255\n", c.nx, c.ny);
+  for (int iy = c.ny - 1; iy >= 0; iy--)
+    if (fwrite(c.cost.data() + (size_t)iy * c.nx, 1, (size_t)c.nx, f) != (size_t)c.nx) {
+      fclose(f);
+      return false;
+    }
+  if (fclose(f) != 0) return false;
+  const size_t slash = prefix.find_last_of('/');
+  f = fopen((prefix + ".yaml").c_str(), "w");
+  if (!f) return false;
+  fprintf(f, "image: %s.pgm\nresolution: %.17g\norigin: [%.17g, %.17g, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n",
+          prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), c.res, c.x0, c.y0);
+  return fclose(f) == 0;
+}
 
 class NodeCore {
  public:
@@ -404,6 +433,28 @@ class NodeCore {
     g.summary = r.summary;
     g.params = q;
     return g;
+  }
+
+  // The costmap of g (vg_clearance): cost and dist2 with g's geometry. inscribed, inflation: metres; scaling:
+  // 1/m; flags bit 0: unknown cells are obstacles too. on_device: g is what occupancy_grid() returned last and
+  // no vg_occupancy ran on the context since, so the grid is read where that call left it and nothing is uploaded.
+  // Completes outstanding work.
+  Costmap costmap(const OccupancyGrid& g, double inscribed, double inflation, double scaling, int flags = 0,
+                  bool on_device = false) {
+    finish();
+    Costmap c;
+    vg_clr_params q = {};
+    q.nx = c.nx = g.nx, q.ny = c.ny = g.ny, q.res = c.res = g.res;
+    c.x0 = g.x0, c.y0 = g.y0;
+    q.flags = flags;
+    q.inscribed_radius = inscribed, q.inflation_radius = inflation, q.cost_scaling = scaling;
+    if (!on_device && g.data.size() != (size_t)g.nx * (size_t)g.ny) throw Error(VG_E_ARG, "costmap: the grid's data is not nx ny cells");
+    LioCore::Clearance r = lio_.clearance(on_device ? nullptr : g.data.data(), q, true, false, true);
+    c.cost = std::move(r.cost);
+    c.dist2 = std::move(r.dist2);
+    c.summary = r.summary;
+    c.params = q;
+    return c;
   }
 
   bool write_tum(const std::string& file) {

@@ -139,6 +139,7 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
   int* d_occ = b.planes + cells;
   const int slab = kInfoSlab;  // (slab D <= 2^24 lanes per launch)
   b.ms = 0.0;
+  b.nx = b.ny = 0;  // (no grid to hand to vg_clearance until this call has finished)
   VG_HIP(hipMemsetAsync(b.planes, 0, 2 * cells * sizeof(int), s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_occ_summary), s));
   if (M > 0) VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -165,6 +166,7 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
   VG_HIP(hipStreamSynchronize(s));
   VG_TRY(occ_elapsed(ctx));
   out->n_rays = (int64_t)M * (int64_t)D;
+  b.nx = prm->nx, b.ny = prm->ny;
   return VG_OK;
 }
 

@@ -430,9 +430,29 @@ struct OccBufs {
   int8_t* grid = nullptr;  // cells
   void* sum = nullptr;     // one vg_occ_summary
   size_t cells = 0;        // capacity of planes / grid, in cells
+  int nx = 0, ny = 0;      // the grid the last call left in `grid` (0: none yet); vg_clearance's grid == NULL reads it
   bool ready = false;      // pos, dirs, sum and the events exist
   hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
   double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_occ_ms)
+};
+// vg_clearance staging (clearance.hip), allocated on first use and grown to the
+// largest grid asked for, freed by vg_destroy (clr_free). dist2 / nearest / cost
+// exist only once a call asked for that output
+struct ClrBufs {
+  int8_t* grid = nullptr;    // cells: a host grid's upload (grid == NULL reads OccBufs::grid instead)
+  int16_t* dy = nullptr;     // cells: k_clr_cols' plane, oy - iy of the column's nearest obstacle (kClrNone: none)
+  int* dist2 = nullptr;      // cells
+  int* nearest = nullptr;    // cells
+  uint8_t* cost = nullptr;   // cells
+  uint8_t* table = nullptr;  // the cost by dist2, table_n entries
+  void* sum = nullptr;       // one vg_clr_summary
+  size_t cells = 0;          // capacity of grid / dy, and of the three outputs where they exist
+  size_t table_cap = 0;      // capacity of table, in entries
+  int table_n = 0;           // entries in use; 0: none built yet
+  double table_key[4] = {0, 0, 0, 0};  // res, inscribed_radius, inflation_radius, cost_scaling the table was built from
+  bool ready = false;        // sum and the events exist
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the call's kernels
+  double ms = 0.0;           // the last call's kernels (vgx_clr_ms)
 };
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
@@ -617,6 +637,7 @@ struct vg_ctx {
   vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
   vg::InfoBufs info;         // vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
   vg::OccBufs occ;           // vg_occupancy staging and count planes (occupancy.hip), allocated on first use
+  vg::ClrBufs clr;           // vg_clearance staging and planes (clearance.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -1022,6 +1043,14 @@ void info_free(vg_ctx* ctx);
 int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
                   const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
 void occ_free(vg_ctx* ctx);
+// clearance.hip: the clearance field and costmap of an nx x ny grid (host grid in, or null: the grid the last
+// vg_occupancy left on the device; dist2, nearest, cost (each or null) and summary out; synchronous on the
+// context stream, which the caller drained). prm: checked by the caller; table: the cost by dist2, table_n
+// entries (dist2 >= table_n costs 0), or null where clr_table_current says the device's is that table
+bool clr_table_current(const vg_ctx* ctx, const vg_clr_params* prm, int table_n);
+int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, const uint8_t* table, int table_n,
+                  int32_t* dist2, int32_t* nearest, uint8_t* cost, vg_clr_summary* out);
+void clr_free(vg_ctx* ctx);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 void change_free(ChangeLayer* L);
@@ -1057,6 +1086,9 @@ int host_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, c
 // occupancy_host.cpp: the call behind the C-ABI
 int host_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D, const vg_occ_params* prm,
                    int8_t* grid, int32_t* counts, vg_occ_summary* out);
+// clearance_host.cpp: the call behind the C-ABI
+int host_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, int32_t* dist2, int32_t* nearest,
+                   uint8_t* cost, vg_clr_summary* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

@@ -15,7 +15,8 @@
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
-//         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]]]
+//         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
+//          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
@@ -53,6 +54,11 @@
 // (image, resolution, origin: [x0, y0, 0], negate: 0, occupied_thresh: 0.65, free_thresh: 0.196). Leaves
 // without a plane are not obstacles in this grid. --occ-rays FILE: what was cast, int32 M, int32 D, the
 // vg_occ_params used, double origins[3 M], double dirs[3 D], to check the grid against the API.
+// --costmap CPREFIX (with --occupancy): straight after the occupancy call the clearance field of that grid is
+// taken where it lies on the device (NodeCore::costmap: vg_clearance with grid == NULL) with the robot's
+// --inscribed r and --inflation R radii in metres (defaults 0.3, 1.0) and --cost-scaling s per metre (default
+// 3.0; nav2's cost_scaling_factor), and its cost written as raw bytes (254 lethal, 253 inscribed, 252 .. 1 the
+// skirt, 0 free, 255 no information) to CPREFIX.pgm, flipped as PREFIX.pgm is, with the same CPREFIX.yaml.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -65,8 +71,8 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
-  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays;
-  double occ_res = 0.1;
+  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix;
+  double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0;
   int ck_at = -1;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
   double places_step = 1.0;
@@ -83,6 +89,10 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--occupancy") occ_prefix = argv0[++i];
     else if (i + 1 < argc0 && a == "--occ-res") occ_res = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--occ-rays") occ_rays = argv0[++i];
+    else if (i + 1 < argc0 && a == "--costmap") cm_prefix = argv0[++i];
+    else if (i + 1 < argc0 && a == "--inscribed") cm_inscribed = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--inflation") cm_inflation = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--cost-scaling") cm_scaling = atof(argv0[++i]);
     else if (a == "--localize") localize = true;
     else if (a == "--global") global = true;
     else if (a == "--scan-diff") scan_diff = true;
@@ -98,6 +108,10 @@ int main(int argc0, char** argv0) {
   }
   if ((!occ_rays.empty() && occ_prefix.empty()) || !(occ_res > 0.0)) {
     fprintf(stderr, "%s: --occ-rays needs --occupancy PREFIX, --occ-res a positive edge\n", argv0[0]);
+    return 2;
+  }
+  if (!cm_prefix.empty() && (occ_prefix.empty() || !(cm_inscribed >= 0.0) || !(cm_inflation >= cm_inscribed) || !(cm_scaling >= 0.0))) {
+    fprintf(stderr, "%s: --costmap needs --occupancy PREFIX, 0 <= --inscribed <= --inflation and --cost-scaling >= 0\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -377,6 +391,18 @@ int main(int argc0, char** argv0) {
       fprintf(stderr, "occupancy: %d x %d cells of %g m from %d origins x %d directions: %lld occupied, %lld free, %lld unknown\n",
               og.nx, og.ny, og.res, (int)(og.origins.size() / 3), (int)(og.dirs.size() / 3), (long long)sm.cells_occupied,
               (long long)sm.cells_free, (long long)sm.cells_unknown);
+      if (!cm_prefix.empty()) {
+        const vina_gpu::Costmap cm = node.costmap(og, cm_inscribed, cm_inflation, cm_scaling, 0, true);
+        if (!vina_gpu::write_costmap(cm_prefix, cm)) {
+          perror("costmap");
+          return 1;
+        }
+        const vg_clr_summary& cs = cm.summary;
+        fprintf(stderr, "costmap: inscribed %g m, inflation %g m, scaling %g /m: %lld obstacles, %lld lethal, %lld inscribed, %lld inflated, %lld free, %lld no information; max dist2 %lld\n",
+                cm_inscribed, cm_inflation, cm_scaling, (long long)cs.n_obstacles, (long long)cs.cells_lethal,
+                (long long)cs.cells_inscribed, (long long)cs.cells_inflated, (long long)cs.cells_free,
+                (long long)cs.cells_no_info, (long long)cs.max_dist2);
+      }
       if (!occ_rays.empty()) {
         const int32_t md[2] = {(int32_t)(og.origins.size() / 3), (int32_t)(og.dirs.size() / 3)};
         FILE* fr = fopen(occ_rays.c_str(), "wb");

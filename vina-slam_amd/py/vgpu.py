@@ -149,6 +149,23 @@ class OccSummary(ctypes.Structure):
                 ("cells_occupied", ctypes.c_int64), ("cells_unknown", ctypes.c_int64), ("reserved", ctypes.c_int64 * 5)]
 
 
+class ClrParams(ctypes.Structure):
+    """vg_clr_params, 80 bytes."""
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("res", ctypes.c_double), ("flags", ctypes.c_int),
+                ("pad", ctypes.c_int), ("inscribed_radius", ctypes.c_double), ("inflation_radius", ctypes.c_double),
+                ("cost_scaling", ctypes.c_double), ("reserved", ctypes.c_double * 4)]
+
+
+class ClrSummary(ctypes.Structure):
+    """vg_clr_summary, 128 bytes."""
+    _fields_ = [("n_obstacles", ctypes.c_int64), ("n_unknown", ctypes.c_int64), ("cells_lethal", ctypes.c_int64),
+                ("cells_inscribed", ctypes.c_int64), ("cells_inflated", ctypes.c_int64), ("cells_free", ctypes.c_int64),
+                ("cells_no_info", ctypes.c_int64), ("max_dist2", ctypes.c_int64), ("reserved", ctypes.c_int64 * 8)]
+
+
+CLR_NONE = 2 ** 31 - 1
+CLR_MAX_SIDE = 32768
+COST_FREE, COST_INSCRIBED, COST_LETHAL, COST_NO_INFO = 0, 253, 254, 255
 OCC_UNKNOWN, OCC_FREE, OCC_OCCUPIED = -1, 0, 100
 OCC_MAX_CELLS = 1 << 24
 OCC_PGM = {OCC_OCCUPIED: 0, OCC_FREE: 254, OCC_UNKNOWN: 205}   # map_server's grey levels
@@ -200,6 +217,32 @@ def write_occupancy(prefix, grid, x0, y0, res):
     with open(prefix + ".yaml", "w") as f:
         f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
                 % (os.path.basename(prefix) + ".pgm", float(res), float(x0), float(y0)))
+
+
+def write_costmap(prefix, cost, x0, y0, res):
+    """The cost (uint8 [ny, nx], COST_*) as raw bytes in prefix.pgm (P5, the first row at the largest y) and
+    write_occupancy's prefix.yaml."""
+    c = np.asarray(cost, dtype=np.uint8)
+    with open(prefix + ".pgm", "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (c.shape[1], c.shape[0]))
+        f.write(np.ascontiguousarray(c[::-1]).tobytes())
+    with open(prefix + ".yaml", "w") as f:
+        f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
+                % (os.path.basename(prefix) + ".pgm", float(res), float(x0), float(y0)))
+
+
+def read_costmap(prefix):
+    """(cost uint8 [ny, nx], x0, y0, res) back from write_costmap's (or vg_node_replay --costmap's) pair."""
+    meta = {}
+    for ln in open(prefix + ".yaml"):
+        k, _, v = ln.partition(":")
+        meta[k.strip()] = v.strip()
+    org = [float(x) for x in meta["origin"].strip("[]").split(",")]
+    raw = open(os.path.join(os.path.dirname(prefix), meta["image"]), "rb").read()
+    m = re.match(rb"P5\s+(\d+)\s+(\d+)\s+255\s", raw)
+    nx, ny = int(m.group(1)), int(m.group(2))
+    c = np.frombuffer(raw, dtype=np.uint8, offset=m.end(), count=nx * ny).reshape(ny, nx)[::-1]
+    return np.ascontiguousarray(c), org[0], org[1], float(meta["resolution"])
 
 
 def read_occupancy(prefix):
@@ -483,6 +526,10 @@ def lib():
             L.vg_occupancy.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(OccParams), P, P,
                                        ctypes.POINTER(OccSummary)]
             L.vgx_occ_ms.argtypes = [P, dp]
+        L.has_clearance = hasattr(L, "vg_clearance")  # a build older than the clearance field (A/B runs)
+        if L.has_clearance:
+            L.vg_clearance.argtypes = [P, P, ctypes.POINTER(ClrParams), P, P, P, ctypes.POINTER(ClrSummary)]
+            L.vgx_clr_ms.argtypes = [P, dp]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -893,6 +940,45 @@ class Context:
         """Device time (ms) of the last occupancy call's kernels, summed over its slabs and the classification."""
         ms = ctypes.c_double(0)
         self._chk(lib().vgx_occ_ms(self.h, ctypes.byref(ms)), "vgx_occ_ms")
+        return ms.value
+
+    # ---- the clearance field and costmap (vina_gpu.h "Clearance field and costmap")
+    def clearance(self, grid=None, *, nx=None, ny=None, res, flags=0, inscribed_radius=0.0, inflation_radius=0.0,
+                  cost_scaling=0.0, want=("dist2", "nearest", "cost")):
+        """vg_clearance of grid (int8 [ny, nx] of OCC_*; None: the grid the last occupancy() call on this
+        context left on the device, nx and ny naming its shape). want: which of dist2 (int32, cells squared,
+        CLR_NONE without any obstacle), nearest (int32, the obstacle's linear index, -1 without any) and cost
+        (uint8, COST_*) leave the device. Returns ({name: array [ny, nx]}, the summary as a dict)."""
+        if not lib().has_clearance:
+            raise VgError("this libvina_gpu.so has no clearance field (vg_clearance): rebuild it")
+        g = None
+        if grid is not None:
+            g = np.ascontiguousarray(grid, dtype=np.int8)
+            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
+                raise ValueError("clearance: grid is [ny, nx]")
+            ny, nx = g.shape
+        elif nx is None or ny is None:
+            raise ValueError("clearance: grid=None needs nx and ny")
+        unknown = [w for w in want if w not in ("dist2", "nearest", "cost")]
+        if unknown:
+            raise ValueError("clearance: want holds %r" % unknown)
+        p = ClrParams()
+        p.nx, p.ny, p.res, p.flags = int(nx), int(ny), res, flags
+        p.inscribed_radius, p.inflation_radius, p.cost_scaling = inscribed_radius, inflation_radius, cost_scaling
+        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        shape = (p.ny, p.nx) if legal else (1, 1)
+        out = {w: np.zeros(shape, dtype=np.uint8 if w == "cost" else np.int32) for w in ("dist2", "nearest", "cost")
+               if w in want}
+        s = ClrSummary()
+        self._chk(lib().vg_clearance(self.h, None if g is None else g.ctypes.data, ctypes.byref(p),
+                                     *[out[w].ctypes.data if w in out else None for w in ("dist2", "nearest", "cost")],
+                                     ctypes.byref(s)), "vg_clearance")
+        return out, {f: int(getattr(s, f)) for f, _ in ClrSummary._fields_ if f != "reserved"}
+
+    def clearance_ms(self):
+        """Device time (ms) of the last clearance call's two kernels."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_clr_ms(self.h, ctypes.byref(ms)), "vgx_clr_ms")
         return ms.value
 
     # ---- the change layer (vina_gpu.h "Change layer")
