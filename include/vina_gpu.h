@@ -707,6 +707,94 @@ typedef struct vg_clr_summary {   /* 128 bytes, no implicit padding */
 int vg_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm,
                  int32_t* dist2, int32_t* nearest, uint8_t* cost, vg_clr_summary* out);
 
+/* ---- Navigation function: cost-to-go over the costmap, and the paths down it ----
+ * nav2's NavFn on the device: the minimum cost-to-go from every cell of an nx x ny
+ * cost plane (uint8, the VG_COST_* values of vg_clearance, i = iy nx + ix) to the
+ * nearest of a set of goal cells, and the paths that descend it. One field serves
+ * every robot heading for the same goals. Everything is integer arithmetic, so the
+ * outputs are a pure function of the inputs and equal a host Dijkstra bit for bit.
+ *
+ * A 256-entry uint16 table trav turns a cost byte into the price of standing on a
+ * cell; trav[c] == 0 means impassable. The default table, filled on the host:
+ *   trav[c]   = neutral + (int)floor(factor c)   for c < lethal_from,
+ *   trav[c]   = 0                                for lethal_from <= c <= 254,
+ *   trav[255] = 0, or with flags bit 0 trav[unknown_as].
+ * The graph: the 8-connected grid over the passable cells. An edge a-b exists only
+ * if both cells are passable and, for a diagonal step, both cells it squeezes
+ * between, (ay, bx) and (by, ax), are passable too (no corner cutting). Its weight
+ *   w(a, b) = K (trav[cost[a]] + trav[cost[b]]),  K = VG_NAV_K_ORTHO (12) for an
+ * orthogonal and VG_NAV_K_DIAG (17) for a diagonal step (17 / 12 ~ sqrt 2), is
+ * symmetric, so the field from the goals is also the cost to them.
+ *
+ * The goals: n_goals cells (ix, iy). One outside the grid or on an impassable cell
+ * is ignored and counted. With D(i) the shortest-path weight from cell i to the
+ * nearest used goal, as a mathematical integer,
+ *   pot[i] = min(D(i), VG_NAV_SAT), and VG_NAV_UNREACHED where no path exists or
+ *            the cell is impassable.
+ * Every relaxation adds with saturation at VG_NAV_SAT; saturation is monotone, so
+ * the fixed point of saturating relaxations is exactly min(D, VG_NAV_SAT).
+ *
+ * A path starts at a start cell c with pot[c] < VG_NAV_UNREACHED and repeats: among
+ * the neighbours n joined to c by an edge with pot[n] < pot[c], step to the one
+ * minimising pot[n] + w(c, n) (64-bit), among equals the smallest linear index;
+ * stop when pot[c] == 0. pot strictly falls, so a walk ends within nx ny steps. */
+#define VG_NAV_SAT        0xFFFFFFFEu   /* pot: the cost-to-go is this or more */
+#define VG_NAV_UNREACHED  0xFFFFFFFFu   /* pot: impassable, or no path to any used goal */
+#define VG_NAV_K_ORTHO 12
+#define VG_NAV_K_DIAG  17
+#define VG_NAV_MAX_POINTS 65536         /* n_goals, n_starts <= this */
+#define VG_NAV_MAX_PATH_CELLS (1 << 27) /* n_starts max_len <= this */
+#define VG_NAV_REACHED   0   /* the path's last cell is a goal */
+#define VG_NAV_NO_PATH   1   /* the start is outside the grid, impassable or unreached; len 0 */
+#define VG_NAV_TRUNCATED 2   /* max_len cells were written before a goal */
+#define VG_NAV_STUCK     3   /* no strictly lower neighbour: only inside a saturated plateau */
+typedef struct vg_nav_params {   /* 64 bytes, no implicit padding */
+  int    nx, ny;        /* as vg_clr_params; nx ny <= VG_OCC_MAX_CELLS, each <= VG_CLR_MAX_SIDE */
+  int    flags;         /* bit 0: an unknown cell (255) is passable at trav[unknown_as] */
+  int    neutral;       /* 0: 50 (nav2's neutral_cost); else >= 1 */
+  int    lethal_from;   /* 0: 253; else 1 .. 255: cost bytes from here to 254 are impassable */
+  int    unknown_as;    /* 0 .. 254: the cost byte an unknown cell is priced as (flags bit 0) */
+  double factor;        /* 0: 0.8 (nav2's cost_factor); else finite, > 0 */
+  double reserved[4];
+} vg_nav_params;
+typedef struct vg_nav_summary {   /* 128 bytes, no implicit padding */
+  int64_t n_goals_used, n_goals_ignored;  /* they sum to n_goals (a cell named twice counts twice) */
+  int64_t cells_passable;                 /* cells with trav[cost] > 0 */
+  int64_t cells_reached;                  /* cells with pot < VG_NAV_UNREACHED (the saturated ones among them) */
+  int64_t cells_saturated;                /* cells with pot == VG_NAV_SAT */
+  int64_t max_pot;                        /* the largest pot of a reached cell; 0 when none is reached */
+  int64_t rounds, tile_runs;              /* relaxation rounds launched and tiles relaxed in them: these two
+                                             depend on scheduling and are not reproducible; every other
+                                             field is a pure function of the input */
+  int64_t reserved[8];
+} vg_nav_summary;
+/* cost: nx ny uint8 on the host, or NULL: the cost plane that the last vg_clearance
+ * call on this context left on the device, of which nothing is uploaded
+ * (VG_E_STATE when no call produced one or its nx, ny differ from prm's). trav: 256
+ * uint16, or NULL: the default table of prm (an explicit table makes neutral,
+ * lethal_from, unknown_as, factor and flags bit 0 irrelevant; their ranges are
+ * still checked, the default table's overflow is not, no such table being
+ * built). goals: n_goals pairs (ix, iy). pot: nx ny uint32, or NULL: the field is
+ * not copied out. It stays on the device for vg_nav_paths until the next vg_navfn
+ * call or vg_destroy. NULL ctx, prm, goals or out; nx or ny < 1 or >
+ * VG_CLR_MAX_SIDE, or nx ny > VG_OCC_MAX_CELLS; n_goals < 1 or > VG_NAV_MAX_POINTS;
+ * flags with a bit above 0; neutral < 0; lethal_from < 0 or > 255; unknown_as < 0
+ * or > 254; factor negative or not finite; a default-table entry above 65535:
+ * VG_E_ARG, and nothing is written. The relaxation is iterated from the host to
+ * its fixed point, at most nx ny + 2 rounds; were that cap ever hit the call
+ * returns VG_E_CAPACITY and leaves no field. Legal where vg_clearance is. */
+int vg_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const uint16_t* trav,
+             const int32_t* goals, int n_goals, uint32_t* pot, vg_nav_summary* out);
+/* Paths down the field of the last vg_navfn call on this context (VG_E_STATE
+ * without one). starts: n_starts pairs (ix, iy). cells: n_starts rows of max_len
+ * int32, row s holding the linear indices of path s from its start on, len[s] of
+ * them, the rest -1. status: VG_NAV_* per start. path_cost (or NULL): pot[start]
+ * per start, -1 with VG_NAV_NO_PATH. NULL ctx, starts, cells, len or status;
+ * n_starts < 1 or > VG_NAV_MAX_POINTS; max_len < 1; n_starts max_len >
+ * VG_NAV_MAX_PATH_CELLS: VG_E_ARG, and nothing is written. */
+int vg_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells,
+                 int32_t* len, int32_t* status, int64_t* path_cost);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

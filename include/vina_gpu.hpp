@@ -193,6 +193,40 @@ class LioCore {
           "vg_clearance");
     return r;
   }
+  // the navigation function (vina_gpu.h "Navigation function") over cost (nx ny cells of VG_COST_*; null: the plane
+  // the last clearance() call left on the device) towards goals (ix, iy pairs); trav null: prm's default table
+  struct NavField {
+    std::vector<uint32_t> pot;  // filled only where asked for
+    vg_nav_summary summary;
+  };
+  NavField navfn(const uint8_t* cost, const vg_nav_params& prm, const std::vector<int32_t>& goals, bool want_pot = true,
+                 const uint16_t* trav = nullptr) {
+    NavField r;
+    size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    if (cells > (size_t)VG_OCC_MAX_CELLS) cells = 1;
+    if (want_pot) r.pot.resize(cells);
+    check(vg_navfn(ctx_, cost, &prm, trav, goals.data(), (int)(goals.size() / 2), want_pot ? r.pot.data() : nullptr,
+                   &r.summary),
+          "vg_navfn");
+    return r;
+  }
+  // the paths from starts (ix, iy pairs) down the field of the last navfn() call: max_len cells a row
+  struct NavPaths {
+    int max_len = 0;
+    std::vector<int32_t> cells, len, status;  // cells: row s at s max_len, -1 past len[s]
+    std::vector<int64_t> cost;                // pot[start]; -1 with VG_NAV_NO_PATH
+  };
+  NavPaths nav_paths(const std::vector<int32_t>& starts, int max_len) {
+    NavPaths r;
+    const size_t n = starts.size() / 2;
+    const bool legal = n >= 1 && n <= (size_t)VG_NAV_MAX_POINTS && max_len >= 1 && n * (size_t)max_len <= (size_t)VG_NAV_MAX_PATH_CELLS;
+    r.max_len = max_len;
+    r.cells.resize(legal ? n * (size_t)max_len : 1);
+    r.len.resize(n ? n : 1), r.status.resize(n ? n : 1), r.cost.resize(n ? n : 1);
+    check(vg_nav_paths(ctx_, starts.data(), (int)n, max_len, r.cells.data(), r.len.data(), r.status.data(), r.cost.data()),
+          "vg_nav_paths");
+    return r;
+  }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
   // owner or any tracker attached to it; prm / q null: the defaults
   void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }

@@ -151,6 +151,15 @@ inline bool write_costmap(const std::string& prefix, const Costmap& c) {
           prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), c.res, c.x0, c.y0);
   return fclose(f) == 0;
 }
+// A planned path (NodeCore::plan): the world polyline through the centres of the path's cells, the start first
+struct Plan {
+  int status = VG_NAV_NO_PATH;   // VG_NAV_*
+  int64_t cost = -1;             // the start's cost-to-go; -1 with VG_NAV_NO_PATH
+  std::vector<int32_t> cells;    // linear indices iy nx + ix
+  std::vector<double> xy;        // x, y per cell, metres
+  std::vector<uint32_t> pot;     // the cost-to-go per cell of the path (plan() with want_pot; else empty)
+  vg_nav_summary summary = {};
+};
 
 class NodeCore {
  public:
@@ -454,7 +463,41 @@ class NodeCore {
     c.dist2 = std::move(r.dist2);
     c.summary = r.summary;
     c.params = q;
+    cm_x0_ = c.x0, cm_y0_ = c.y0, cm_res_ = c.res, cm_nx_ = c.nx, cm_ny_ = c.ny;
     return c;
+  }
+
+  // The path from start_xy to goal_xy (world metres) over the last costmap() of this node, whose cost plane is read
+  // where vg_clearance left it on the device (no vg_clearance may have run on the context since): vg_navfn towards
+  // the goal's cell with prm's traversal table (null: nav2's defaults), then vg_nav_paths from the start's cell,
+  // at most max_len cells. want_pot: the field is downloaded to fill Plan::pot. Further starts towards the same
+  // goal: lio().nav_paths(). Completes outstanding work.
+  Plan plan(const double goal_xy[2], const double start_xy[2], const vg_nav_params* prm = nullptr, int max_len = 65536,
+            bool want_pot = false) {
+    finish();
+    if (!cm_nx_) throw Error(VG_E_STATE, "plan: no costmap() on this node yet");
+    vg_nav_params q = {};
+    if (prm) q = *prm;
+    q.nx = cm_nx_, q.ny = cm_ny_;
+    // the cell holding a world point; -1 (outside every grid) where the point is off the grid, far off or not a
+    // number, so that no double beyond int32 is ever converted
+    const auto index = [](double v, int n) { return v >= 0.0 && v < (double)n ? (int32_t)v : (int32_t)-1; };
+    const auto cell = [&](const double* xy) {
+      return std::vector<int32_t>{index(std::floor((xy[0] - cm_x0_) / cm_res_), cm_nx_),
+                                  index(std::floor((xy[1] - cm_y0_) / cm_res_), cm_ny_)};
+    };
+    Plan p;
+    const LioCore::NavField f = lio_.navfn(nullptr, q, cell(goal_xy), want_pot);
+    p.summary = f.summary;
+    const LioCore::NavPaths r = lio_.nav_paths(cell(start_xy), max_len);
+    p.status = r.status[0], p.cost = r.cost[0];
+    p.cells.assign(r.cells.begin(), r.cells.begin() + r.len[0]);
+    for (const int32_t c : p.cells) {
+      p.xy.push_back(cm_x0_ + (c % cm_nx_ + 0.5) * cm_res_);
+      p.xy.push_back(cm_y0_ + (c / cm_nx_ + 0.5) * cm_res_);
+      if (want_pot) p.pot.push_back(f.pot[(size_t)c]);
+    }
+    return p;
   }
 
   bool write_tum(const std::string& file) {
@@ -545,6 +588,8 @@ class NodeCore {
   int reloc_top_k_ = 16;
   vg_place_candidate reloc_place_ = {};
   int publish_ = 0;  // vg_set_publish flags
+  double cm_x0_ = 0, cm_y0_ = 0, cm_res_ = 0;  // the last costmap()'s geometry (plan())
+  int cm_nx_ = 0, cm_ny_ = 0;
   bool visualization_ = false;
   std::function<void()> after_step_;
   std::vector<vg_plane_marker> markers_, marker_buf_;

@@ -172,6 +172,7 @@ static int clr_bufs(vg_ctx* ctx, size_t cells, bool want_dist2, bool want_neares
     if (b.cost) (void)hipFree(b.cost);
     b.grid = nullptr, b.dy = nullptr, b.dist2 = nullptr, b.nearest = nullptr, b.cost = nullptr;
     b.cells = 0;
+    b.nx = b.ny = 0;
     VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.grid), cells));
     VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dy), cells * sizeof(int16_t)));
     b.cells = cells;
@@ -213,6 +214,7 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
   unsigned long long* d_sum = static_cast<unsigned long long*>(b.sum);
   const int8_t* d_grid = grid ? b.grid : ctx->occ.grid;
   b.ms = 0.0;
+  if (cost) b.nx = b.ny = 0;  // (no cost plane to hand to vg_navfn until this call has finished)
   if (table) {
     const double key[4] = {prm->res, prm->inscribed_radius, prm->inflation_radius, prm->cost_scaling};
     b.table_n = 0;
@@ -247,6 +249,7 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
   float t = 0;
   VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
   b.ms = t;
+  if (cost) b.nx = nx, b.ny = ny;
   return VG_OK;
 }
 

@@ -444,6 +444,7 @@ struct ClrBufs {
   int* dist2 = nullptr;      // cells
   int* nearest = nullptr;    // cells
   uint8_t* cost = nullptr;   // cells
+  int nx = 0, ny = 0;        // the plane the last call that asked for `cost` left there (0: none); vg_navfn's cost == NULL reads it
   uint8_t* table = nullptr;  // the cost by dist2, table_n entries
   void* sum = nullptr;       // one vg_clr_summary
   size_t cells = 0;          // capacity of grid / dy, and of the three outputs where they exist
@@ -453,6 +454,29 @@ struct ClrBufs {
   bool ready = false;        // sum and the events exist
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the call's kernels
   double ms = 0.0;           // the last call's kernels (vgx_clr_ms)
+};
+// vg_navfn / vg_nav_paths planes and staging (navfn.hip), allocated on first use
+// and grown to the largest plane asked for, freed by vg_destroy (nav_free)
+struct NavBufs {
+  uint8_t* cost = nullptr;    // cells: a host plane's upload (cost == NULL reads ClrBufs::cost instead)
+  uint16_t* trav = nullptr;   // cells: the price of standing on the cell, 0 impassable (k_nav_init)
+  uint32_t* pot = nullptr;    // cells: the field
+  size_t cells = 0;           // capacity of cost / trav / pot, in cells
+  int* act = nullptr;         // two activity planes of act_cap tiles each: this round's and the next's
+  size_t act_cap = 0;
+  uint16_t* table = nullptr;  // 256 entries: trav by cost byte
+  int* goals = nullptr;       // 2 kNavMaxPoints: goals (vg_navfn) or starts (vg_nav_paths)
+  unsigned* marks = nullptr;  // kNavBatchMax counters, one per round of a batch: tiles that woke a neighbour
+  void* sum = nullptr;        // one vg_nav_summary
+  int* cells_out = nullptr;   // vg_nav_paths: n_starts max_len path cells
+  size_t cells_out_cap = 0;
+  int* len = nullptr;         // kNavMaxPoints each: len, status; path_cost
+  int* status = nullptr;
+  long long* path_cost = nullptr;
+  int nx = 0, ny = 0;         // the field the last vg_navfn call left in `pot` (0: none)
+  bool ready = false;         // table, goals, marks, sum, len, status, path_cost and the events exist
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the call's kernels
+  double ms = 0.0;            // the last call's kernels (vgx_nav_ms)
 };
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
@@ -638,6 +662,7 @@ struct vg_ctx {
   vg::InfoBufs info;         // vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
   vg::OccBufs occ;           // vg_occupancy staging and count planes (occupancy.hip), allocated on first use
   vg::ClrBufs clr;           // vg_clearance staging and planes (clearance.hip), allocated on first use
+  vg::NavBufs nav;           // vg_navfn / vg_nav_paths planes (navfn.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -1051,6 +1076,14 @@ bool clr_table_current(const vg_ctx* ctx, const vg_clr_params* prm, int table_n)
 int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, const uint8_t* table, int table_n,
                   int32_t* dist2, int32_t* nearest, uint8_t* cost, vg_clr_summary* out);
 void clr_free(vg_ctx* ctx);
+// navfn.hip: the navigation function of an nx x ny cost plane (host plane in, or null: the plane the last
+// vg_clearance left on the device; pot (or null) and summary out) and the paths down the field it left; synchronous
+// on the context stream, which the caller drained. Arguments: checked by the caller; table: trav by cost byte
+int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const uint16_t* table, const int32_t* goals,
+              int n_goals, uint32_t* pot, vg_nav_summary* out);
+int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
+                  int32_t* status, int64_t* path_cost);
+void nav_free(vg_ctx* ctx);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 void change_free(ChangeLayer* L);
@@ -1089,6 +1122,11 @@ int host_occupancy(vg_ctx* ctx, const double* positions, int M, const double* di
 // clearance_host.cpp: the call behind the C-ABI
 int host_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, int32_t* dist2, int32_t* nearest,
                    uint8_t* cost, vg_clr_summary* out);
+// navfn_host.cpp: the calls behind the C-ABI
+int host_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const uint16_t* trav, const int32_t* goals,
+               int n_goals, uint32_t* pot, vg_nav_summary* out);
+int host_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
+                   int32_t* status, int64_t* path_cost);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

@@ -335,6 +335,7 @@ int vg_destroy(vg_ctx* ctx) {
   info_free(ctx);
   occ_free(ctx);
   clr_free(ctx);
+  nav_free(ctx);
   shard_free(ctx);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);

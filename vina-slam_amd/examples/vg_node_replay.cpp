@@ -16,7 +16,8 @@
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
 //         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
-//          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]]]]
+//          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]
+//           [--plan "gx gy" [--from "sx sy"] --path out.csv]]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
@@ -59,6 +60,11 @@
 // --inscribed r and --inflation R radii in metres (defaults 0.3, 1.0) and --cost-scaling s per metre (default
 // 3.0; nav2's cost_scaling_factor), and its cost written as raw bytes (254 lethal, 253 inscribed, 252 .. 1 the
 // skirt, 0 free, 255 no information) to CPREFIX.pgm, flipped as PREFIX.pgm is, with the same CPREFIX.yaml.
+// --plan "gx gy" (with --costmap): the navigation function over that costmap where it lies on the device
+// (NodeCore::plan: vg_navfn with cost == NULL, nav2's default traversal table) towards the cell holding the
+// world point gx gy, and the path down it from the cell holding --from "sx sy" (default: the last pose), written
+// to --path out.csv as one x,y,pot row per cell (the cell's centre in metres, its cost-to-go), the start first.
+// One line on stdout: the status (REACHED, NO_PATH, TRUNCATED, STUCK), the number of cells and the start's cost.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -71,7 +77,8 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
-  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix;
+  std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix, plan_s, from_s,
+      plan_csv;
   double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0;
   int ck_at = -1;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
@@ -90,6 +97,9 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--occ-res") occ_res = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--occ-rays") occ_rays = argv0[++i];
     else if (i + 1 < argc0 && a == "--costmap") cm_prefix = argv0[++i];
+    else if (i + 1 < argc0 && a == "--plan") plan_s = argv0[++i];
+    else if (i + 1 < argc0 && a == "--from") from_s = argv0[++i];
+    else if (i + 1 < argc0 && a == "--path") plan_csv = argv0[++i];
     else if (i + 1 < argc0 && a == "--inscribed") cm_inscribed = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--inflation") cm_inflation = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--cost-scaling") cm_scaling = atof(argv0[++i]);
@@ -112,6 +122,13 @@ int main(int argc0, char** argv0) {
   }
   if (!cm_prefix.empty() && (occ_prefix.empty() || !(cm_inscribed >= 0.0) || !(cm_inflation >= cm_inscribed) || !(cm_scaling >= 0.0))) {
     fprintf(stderr, "%s: --costmap needs --occupancy PREFIX, 0 <= --inscribed <= --inflation and --cost-scaling >= 0\n", argv0[0]);
+    return 2;
+  }
+  double plan_goal[2] = {0, 0}, plan_from[2] = {0, 0};
+  if ((!plan_s.empty() || !from_s.empty() || !plan_csv.empty()) &&
+      (cm_prefix.empty() || plan_csv.empty() || sscanf(plan_s.c_str(), "%lf %lf", &plan_goal[0], &plan_goal[1]) != 2 ||
+       (!from_s.empty() && sscanf(from_s.c_str(), "%lf %lf", &plan_from[0], &plan_from[1]) != 2))) {
+    fprintf(stderr, "%s: --plan \"gx gy\" needs --costmap CPREFIX and --path FILE; --from is \"sx sy\"\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -402,6 +419,31 @@ int main(int argc0, char** argv0) {
                 cm_inscribed, cm_inflation, cm_scaling, (long long)cs.n_obstacles, (long long)cs.cells_lethal,
                 (long long)cs.cells_inscribed, (long long)cs.cells_inflated, (long long)cs.cells_free,
                 (long long)cs.cells_no_info, (long long)cs.max_dist2);
+        if (!plan_s.empty()) {
+          if (from_s.empty()) {
+            if (node.tum_rows().empty()) {
+              fprintf(stderr, "plan: no pose to start from; give --from\n");
+              return 1;
+            }
+            plan_from[0] = node.tum_rows().back().p[0], plan_from[1] = node.tum_rows().back().p[1];
+          }
+          const vina_gpu::Plan pl = node.plan(plan_goal, plan_from, nullptr, cm.nx * cm.ny < 65536 ? cm.nx * cm.ny : 65536, true);
+          FILE* fp = fopen(plan_csv.c_str(), "w");
+          if (!fp) {
+            perror("path");
+            return 1;
+          }
+          for (size_t k = 0; k < pl.cells.size(); k++)
+            fprintf(fp, "%.17g,%.17g,%u\n", pl.xy[2 * k], pl.xy[2 * k + 1], pl.pot[k]);
+          if (fclose(fp) != 0) {
+            perror("path");
+            return 1;
+          }
+          static const char* const names[] = {"REACHED", "NO_PATH", "TRUNCATED", "STUCK"};
+          printf("plan: %s, %d cells, cost %lld, from %.17g %.17g to %.17g %.17g; %lld of %lld passable cells reached\n",
+                 names[pl.status & 3], (int)pl.cells.size(), (long long)pl.cost, plan_from[0], plan_from[1], plan_goal[0],
+                 plan_goal[1], (long long)pl.summary.cells_reached, (long long)pl.summary.cells_passable);
+        }
       }
       if (!occ_rays.empty()) {
         const int32_t md[2] = {(int32_t)(og.origins.size() / 3), (int32_t)(og.dirs.size() / 3)};

@@ -5,6 +5,7 @@ loads ONLY the in-tree HIP library; there is no CPU fallback — if the library
 or a GPU is missing every call raises.
 """
 import ctypes
+import math
 import os
 import re
 import subprocess
@@ -163,6 +164,25 @@ class ClrSummary(ctypes.Structure):
                 ("cells_no_info", ctypes.c_int64), ("max_dist2", ctypes.c_int64), ("reserved", ctypes.c_int64 * 8)]
 
 
+class NavParams(ctypes.Structure):
+    """vg_nav_params, 64 bytes."""
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("flags", ctypes.c_int), ("neutral", ctypes.c_int),
+                ("lethal_from", ctypes.c_int), ("unknown_as", ctypes.c_int), ("factor", ctypes.c_double),
+                ("reserved", ctypes.c_double * 4)]
+
+
+class NavSummary(ctypes.Structure):
+    """vg_nav_summary, 128 bytes."""
+    _fields_ = [("n_goals_used", ctypes.c_int64), ("n_goals_ignored", ctypes.c_int64), ("cells_passable", ctypes.c_int64),
+                ("cells_reached", ctypes.c_int64), ("cells_saturated", ctypes.c_int64), ("max_pot", ctypes.c_int64),
+                ("rounds", ctypes.c_int64), ("tile_runs", ctypes.c_int64), ("reserved", ctypes.c_int64 * 8)]
+
+
+NAV_SAT, NAV_UNREACHED = 0xFFFFFFFE, 0xFFFFFFFF
+NAV_K_ORTHO, NAV_K_DIAG = 12, 17
+NAV_MAX_POINTS, NAV_MAX_PATH_CELLS = 65536, 1 << 27
+NAV_REACHED, NAV_NO_PATH, NAV_TRUNCATED, NAV_STUCK = 0, 1, 2, 3
+NAV_SCHEDULING = ("rounds", "tile_runs")    # the summary's fields that depend on scheduling
 CLR_NONE = 2 ** 31 - 1
 CLR_MAX_SIDE = 32768
 COST_FREE, COST_INSCRIBED, COST_LETHAL, COST_NO_INFO = 0, 253, 254, 255
@@ -229,6 +249,28 @@ def write_costmap(prefix, cost, x0, y0, res):
     with open(prefix + ".yaml", "w") as f:
         f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n"
                 % (os.path.basename(prefix) + ".pgm", float(res), float(x0), float(y0)))
+
+
+def nav_trav_table(flags=0, neutral=0, lethal_from=0, unknown_as=0, factor=0.0):
+    """vg_navfn's default traversal table (uint16 [256], 0 impassable) of these parameters, zeros taking nav2's
+    values, as the library fills it (no device); ValueError where the library returns VG_E_ARG."""
+    if (flags & ~1 or neutral < 0 or not 0 <= lethal_from <= 255 or not 0 <= unknown_as <= 254
+            or not (factor >= 0.0 and math.isfinite(factor))):
+        raise ValueError("nav_trav_table: a parameter out of range")
+    neutral, lethal_from, factor = neutral or 50, lethal_from or 253, factor or 0.8
+    t = [neutral + int(math.floor(factor * c)) if c < min(lethal_from, 255) else 0 for c in range(256)]
+    if max(t) > 65535:
+        raise ValueError("nav_trav_table: an entry overflows uint16")
+    if flags & 1:
+        t[255] = t[unknown_as]
+    return np.array(t, dtype=np.uint16)
+
+
+def cells_to_world(cells, nx, x0, y0, res):
+    """(n, 2) world x, y of the centres of the cells with linear indices `cells` (iy nx + ix) of a grid whose
+    cell (0, 0) has its corner at (x0, y0)."""
+    c = np.asarray(cells, dtype=np.int64).reshape(-1)
+    return np.stack([x0 + (c % nx + 0.5) * res, y0 + (c // nx + 0.5) * res], axis=1)
 
 
 def read_costmap(prefix):
@@ -530,6 +572,11 @@ def lib():
         if L.has_clearance:
             L.vg_clearance.argtypes = [P, P, ctypes.POINTER(ClrParams), P, P, P, ctypes.POINTER(ClrSummary)]
             L.vgx_clr_ms.argtypes = [P, dp]
+        L.has_navfn = hasattr(L, "vg_navfn")  # a build older than the navigation function (A/B runs)
+        if L.has_navfn:
+            L.vg_navfn.argtypes = [P, P, ctypes.POINTER(NavParams), P, P, ctypes.c_int, P, ctypes.POINTER(NavSummary)]
+            L.vg_nav_paths.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P]
+            L.vgx_nav_ms.argtypes = [P, dp]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -979,6 +1026,66 @@ class Context:
         """Device time (ms) of the last clearance call's two kernels."""
         ms = ctypes.c_double(0)
         self._chk(lib().vgx_clr_ms(self.h, ctypes.byref(ms)), "vgx_clr_ms")
+        return ms.value
+
+    # ---- the navigation function (vina_gpu.h "Navigation function")
+    def navfn(self, cost=None, goals=(), *, nx=None, ny=None, want_pot=True, trav=None, **params):
+        """vg_navfn over cost (uint8 [ny, nx] of COST_*; None: the cost plane the last clearance() call on this
+        context left on the device, nx and ny naming its shape) towards goals ((G, 2) cells ix, iy). trav: an
+        explicit uint16 [256] table, or None: nav_trav_table(**params) as the library builds it from params
+        (flags, neutral, lethal_from, unknown_as, factor). Returns (pot uint32 [ny, nx] of cost-to-go, NAV_SAT,
+        NAV_UNREACHED, or None without want_pot; the summary as a dict). The field stays on the device for
+        nav_paths()."""
+        if not lib().has_navfn:
+            raise VgError("this libvina_gpu.so has no navigation function (vg_navfn): rebuild it")
+        c = None
+        if cost is not None:
+            c = np.ascontiguousarray(cost, dtype=np.uint8)
+            if c.ndim != 2 or (nx not in (None, c.shape[1])) or (ny not in (None, c.shape[0])):
+                raise ValueError("navfn: cost is [ny, nx]")
+            ny, nx = c.shape
+        elif nx is None or ny is None:
+            raise ValueError("navfn: cost=None needs nx and ny")
+        g = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
+        t = None
+        if trav is not None:
+            t = np.ascontiguousarray(trav, dtype=np.uint16)
+            if t.shape != (256,):
+                raise ValueError("navfn: trav is uint16 [256]")
+        p = NavParams()
+        p.nx, p.ny = int(nx), int(ny)
+        for k, v in params.items():
+            if k not in ("flags", "neutral", "lethal_from", "unknown_as", "factor"):
+                raise ValueError("navfn: no parameter %r" % k)
+            setattr(p, k, v)
+        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        pot = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.uint32) if want_pot else None
+        s = NavSummary()
+        self._chk(lib().vg_navfn(self.h, None if c is None else c.ctypes.data, ctypes.byref(p),
+                                 None if t is None else t.ctypes.data, g.ctypes.data, g.shape[0],
+                                 None if pot is None else pot.ctypes.data, ctypes.byref(s)), "vg_navfn")
+        return pot, {f: int(getattr(s, f)) for f, _ in NavSummary._fields_ if f != "reserved"}
+
+    def nav_paths(self, starts, max_len):
+        """vg_nav_paths from starts ((S, 2) cells ix, iy) down the field of the last navfn() call. Returns
+        (cells int32 [S, max_len] of linear indices, -1 past a path's end; len int32 [S]; status int32 [S] of
+        NAV_REACHED, NAV_NO_PATH, NAV_TRUNCATED, NAV_STUCK; path_cost int64 [S]: pot[start], -1 with NAV_NO_PATH)."""
+        if not lib().has_navfn:
+            raise VgError("this libvina_gpu.so has no navigation function (vg_nav_paths): rebuild it")
+        st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 2)
+        n, m = st.shape[0], int(max_len)
+        legal = 1 <= n <= NAV_MAX_POINTS and m >= 1 and n * m <= NAV_MAX_PATH_CELLS
+        cells = np.zeros((n, m) if legal else (1, 1), dtype=np.int32)
+        ln, status = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        pc = np.zeros(max(n, 1), dtype=np.int64)
+        self._chk(lib().vg_nav_paths(self.h, st.ctypes.data, n, m, cells.ctypes.data, ln.ctypes.data, status.ctypes.data,
+                                     pc.ctypes.data), "vg_nav_paths")
+        return cells, ln, status, pc
+
+    def navfn_ms(self):
+        """Device time (ms) of the last navfn() or nav_paths() call's kernels."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_nav_ms(self.h, ctypes.byref(ms)), "vgx_nav_ms")
         return ms.value
 
     # ---- the change layer (vina_gpu.h "Change layer")
