@@ -66,6 +66,9 @@ def lib():
         L.orc_jour.argtypes = [P]
         L.orc_jour.restype = ctypes.c_double
         L.orc_roots.argtypes = [P, ctypes.POINTER(ctypes.c_longlong), dp, ip, ip, ip, ctypes.c_int]
+        L.orc_map_dump_after_recut.argtypes = [P, ctypes.c_int]
+        L.orc_map_nodes.argtypes = [P, ctypes.c_int, dp, ctypes.c_int, lp]
+        L.orc_map_points.argtypes = [P, ctypes.c_int, dp, lp, dp, lp]
         L.orc_shard.argtypes = [P, ctypes.c_int, ctypes.c_int, ALLREDUCE, P]
         L.orc_step_deskew.argtypes = [P, fp, fp, fp, ctypes.c_int, ctypes.c_double, ctypes.c_double, dp, ctypes.c_int,
                                       dp]
@@ -231,6 +234,30 @@ def _roots_call(fn):
             for i in range(n)}
 
 
+NODE_REC, NODE_SLOT = 131, 11  # vina_oracle.h ORC_NODE_REC / ORC_NODE_SLOT
+
+
+def _map_nodes_call(nodes_fn, points_fn):
+    """The two-call shape of orc_map_nodes / vgx_map_nodes: nodes_fn(rec, cap, info) -> node count,
+    points_fn(fixp, fix_off, winp, win_off). Returns the raw dump (tests/map_dump.py reads it)."""
+    lp = ctypes.POINTER(ctypes.c_int64)
+    info = np.zeros(5 + 32, dtype=np.int64)
+    n = int(nodes_fn(None, 0, info.ctypes.data_as(lp)))
+    assert n >= 0 and n == info[0], (n, info[:5])
+    W = int(info[4])
+    rec = np.zeros((max(n, 1), NODE_REC + NODE_SLOT * W))
+    m = int(nodes_fn(_d(rec), n, info.ctypes.data_as(lp)))
+    assert m == n, (m, n)
+    fixp = np.zeros((max(int(info[1]), 1), 12))
+    winp = np.zeros((max(int(info[2]), 1), 12))
+    fix_off = np.zeros(n + 1, dtype=np.int64)
+    win_off = np.zeros(n * W + 1, dtype=np.int64)
+    points_fn(_d(fixp), fix_off.ctypes.data_as(lp), _d(winp), win_off.ctypes.data_as(lp))
+    assert fix_off[-1] == info[1] and win_off[-1] == info[2], (fix_off[-1], win_off[-1], info[:5])
+    return {"rec": rec[:n], "fixp": fixp[: int(info[1])], "winp": winp[: int(info[2])], "fix_off": fix_off,
+            "win_off": win_off, "win_count": int(info[3]), "W": W, "mp": [int(v) for v in info[5: 5 + W]]}
+
+
 class Pipeline:
     """The reference's per-scan steady-state loop (CPU restatement)."""
 
@@ -311,6 +338,17 @@ class Pipeline:
     def roots(self):
         """Every root voxel: {(x, y, z): (jour stamp, flags 1 in slide | 2 isexist, subtree nodes, point_fix)}."""
         return _roots_call(lambda *a: lib().orc_roots(self.h, *a))
+
+    def map_dump_after_recut(self, on=True):
+        """Every later step keeps a copy of the map dump taken between multi_recut and the window tail."""
+        lib().orc_map_dump_after_recut(self.h, 1 if on else 0)
+
+    def map_nodes(self, after_recut=False):
+        """surf_map node for node (orc_map_nodes; the record layout is in vina_oracle.h): the raw dump
+        of the map as it is now, or of the copy the last step took after multi_recut."""
+        w = 1 if after_recut else 0
+        return _map_nodes_call(lambda rec, cap, info: lib().orc_map_nodes(self.h, w, rec, cap, info),
+                               lambda *a: lib().orc_map_points(self.h, w, *a))
 
     def trajectory(self):
         """save_pose_tum rows (steady-state scans): t, R(9), p(3)."""

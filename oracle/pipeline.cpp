@@ -39,6 +39,15 @@ struct Pipeline {
   orc_stats st;
   std::vector<V3> pwld;
   std::vector<PointType> pl_tree;  // the initialisation map (odometry.cpp:269 pl_tree)
+  // test hook (orc_map_nodes): the node-for-node dump of surf_map, [0] as last
+  // taken, [1] the copy a step takes between multi_recut and the window tail
+  struct MapDump {
+    int n = 0, win_count = 0;
+    std::vector<int> mp;
+    std::vector<double> rec, fixp, winp;
+    std::vector<long long> fix_off, win_off;
+  } dump[2];
+  bool dump_after_recut = false;
 
   // lio_state_estimation_kdtree — odometry.cpp:267-439. Returns
   // the valid correspondence count of the last iteration, or -1 when the map
@@ -546,6 +555,79 @@ struct Pipeline {
     census(out);
   }
 
+  // test hook (orc_map_nodes, layout in vina_oracle.h): every node of every
+  // tree of surf_map, one record each, and its point lists
+  void map_dump_node(MapDump& d, const VOXEL_LOC& key, OctoTree* o, std::vector<int>& path) {
+    const int W = cfg.win_size, R = ORC_NODE_REC + ORC_NODE_SLOT * W;
+    d.rec.resize(d.rec.size() + R, 0.0);
+    double* r = d.rec.data() + d.rec.size() - R;
+    r[0] = (double)key.x; r[1] = (double)key.y; r[2] = (double)key.z;
+    r[3] = (double)path.size();
+    for (int i = 0; i < 8; i++) r[4 + i] = i < (int)path.size() ? path[i] : -1;
+    int mask = 0;
+    for (int i = 0; i < 8; i++)
+      if (o->leaves[i] != nullptr) mask |= 1 << i;
+    r[12] = o->layer; r[13] = o->octo_state; r[14] = o->isexist ? 1 : 0; r[15] = o->plane.is_plane ? 1 : 0;
+    r[16] = mask; r[17] = o->last_num; r[18] = o->opt_state; r[19] = o->sw != nullptr ? 1 : 0;
+    for (int i = 0; i < 3; i++) r[20 + i] = o->voxel_center[i];
+    r[23] = o->quater_length;
+    r[24] = path.empty() ? o->jour : 0.0;
+    auto clu = [](double* q, const PointCluster& c) {
+      q[0] = c.N;
+      for (int i = 0; i < 3; i++) q[1 + i] = c.v[i];
+      int k = 4;
+      for (int i = 0; i < 3; i++)
+        for (int j = i; j < 3; j++) q[k++] = c.P(i, j);
+    };
+    clu(r + 25, o->pcr_fix);
+    clu(r + 35, o->pcr_add);
+    int k = 45;
+    for (int i = 0; i < 9; i++)
+      for (int j = i; j < 9; j++) r[k++] = o->cov_add(i, j);
+    for (int i = 0; i < 3; i++) r[90 + i] = o->plane.center[i];
+    for (int i = 0; i < 3; i++) r[93 + i] = o->plane.normal[i];
+    k = 96;
+    for (int i = 0; i < 6; i++)
+      for (int j = i; j < 6; j++) r[k++] = o->plane.plane_var(i, j);
+    r[117] = o->plane.radius;
+    for (int i = 0; i < 3; i++) r[118 + i] = o->eig_value[i];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) r[121 + 3 * i + j] = o->eig_vector(i, j);
+    r[130] = (double)o->point_fix.size();
+    auto pt = [](std::vector<double>& out, const pointVar& pv) {
+      for (int i = 0; i < 3; i++) out.push_back(pv.pnt[i]);
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) out.push_back(pv.var(i, j));
+    };
+    for (const pointVar& pv : o->point_fix) pt(d.fixp, pv);
+    d.fix_off.push_back((long long)d.fixp.size() / 12);
+    for (int s = 0; s < W; s++) {
+      double* q = r + ORC_NODE_REC + ORC_NODE_SLOT * s;
+      if (o->sw != nullptr && s < (int)o->sw->points.size()) {
+        q[0] = (double)o->sw->points[s].size();
+        clu(q + 1, o->sw->pcrs_local[s]);
+        for (const pointVar& pv : o->sw->points[s]) pt(d.winp, pv);
+      }
+      d.win_off.push_back((long long)d.winp.size() / 12);
+    }
+    d.n++;
+    for (int i = 0; i < 8; i++)
+      if (o->leaves[i] != nullptr) {
+        path.push_back(i);
+        map_dump_node(d, key, o->leaves[i], path);
+        path.pop_back();
+      }
+  }
+  void map_dump(MapDump& d) {
+    d = MapDump();
+    d.win_count = win_count;
+    d.mp = mpar.mp;
+    d.fix_off.push_back(0);
+    d.win_off.push_back(0);
+    std::vector<int> path;
+    for (auto& kv : surf_map) map_dump_node(d, kv.first, kv.second, path);
+  }
+
   // local_mapping.cpp:489-546: with a full window, LI_BA damping_iter, x_curr.R/p
   // from the window's last frame, multi_margi, jour, the mp ring and the slide
   template <class TP>
@@ -675,6 +757,7 @@ struct Pipeline {
     auto t3 = clk::now();
     multi_recut();
     st.n_factors = (int)voxhess.plvec_voxels.size();
+    if (dump_after_recut) map_dump(dump[1]);
     auto t4 = clk::now();
     auto t5 = t4, t6 = t4;
     if (win_count >= cfg.win_size) window_tail(&t5, &t6);
@@ -936,6 +1019,39 @@ int orc_roots(void* h, long long* key, double* jour, int* flags, int* nodes, int
   return n;
 }
 double orc_jour(void* h) { return ((Pipeline*)h)->jour; }
+// test hook: surf_map node for node (layout in vina_oracle.h). which 0: the map
+// as it is now (dumped by this call), 1: the copy the last step took after
+// multi_recut (orc_map_dump_after_recut). info: [0] nodes, [1] point_fix points,
+// [2] window points, [3] win_count, [4] W, [5 .. 5 + W) mp[]. Returns the node
+// count; rec is written when cap holds them all. orc_map_points then gives the
+// points of the dump orc_map_nodes last returned for `which`.
+void orc_map_dump_after_recut(void* h, int on) { ((Pipeline*)h)->dump_after_recut = on != 0; }
+int orc_map_nodes(void* h, int which, double* rec, int cap, long long* info) {
+  Pipeline* P = (Pipeline*)h;
+  if (which != 0 && which != 1) return -1;
+  if (which == 0) P->map_dump(P->dump[0]);
+  const Pipeline::MapDump& d = P->dump[which];
+  if (info) {
+    info[0] = d.n;
+    info[1] = d.fix_off.empty() ? 0 : d.fix_off.back();
+    info[2] = d.win_off.empty() ? 0 : d.win_off.back();
+    info[3] = d.win_count;
+    info[4] = P->cfg.win_size;
+    for (size_t i = 0; i < d.mp.size(); i++) info[5 + i] = d.mp[i];
+  }
+  if (rec && cap >= d.n && d.n > 0) memcpy(rec, d.rec.data(), d.rec.size() * sizeof(double));
+  return d.n;
+}
+int orc_map_points(void* h, int which, double* fixp, long long* fix_off, double* winp, long long* win_off) {
+  Pipeline* P = (Pipeline*)h;
+  if (which != 0 && which != 1) return -1;
+  const Pipeline::MapDump& d = P->dump[which];
+  if (!d.fixp.empty()) memcpy(fixp, d.fixp.data(), d.fixp.size() * sizeof(double));
+  if (!d.winp.empty()) memcpy(winp, d.winp.data(), d.winp.size() * sizeof(double));
+  if (!d.fix_off.empty()) memcpy(fix_off, d.fix_off.data(), d.fix_off.size() * sizeof(long long));
+  if (!d.win_off.empty()) memcpy(win_off, d.win_off.data(), d.win_off.size() * sizeof(long long));
+  return d.n;
+}
 // one lio_state_estimation_kdtree call on the scan downsampled at
 // max(down_size, 0.5) (raw LiDAR frame; var_init applies the extrinsic),
 // with the context's x_curr (orc_seed / orc_get_state) as the state

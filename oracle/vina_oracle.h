@@ -75,6 +75,31 @@ double orc_jour(void* h);
 /* test hook: every root voxel (key x/y/z, jour stamp, flags 1: in the slide map |
  * 2: isexist, subtree nodes, point_fix points); returns the root count */
 int orc_roots(void* h, long long* key, double* jour, int* flags, int* nodes, int* nfix, int cap);
+/* test hook: surf_map node for node (OctoTree, octree.hpp:21-97), for the
+ * comparison with the device map (vgx_map_nodes gives the same record). One
+ * record of ORC_NODE_REC + ORC_NODE_SLOT * W doubles per node, any order:
+ *   [0..2] root key, [3] path length, [4..11] octant path from the root
+ *   (leaves[] indices, -1 past the end), [12] layer, [13] octo_state,
+ *   [14] isexist, [15] plane.is_plane, [16] child mask (bit i: leaves[i]),
+ *   [17] last_num, [18] opt_state, [19] sw != null, [20..22] voxel_center,
+ *   [23] quater_length, [24] jour (roots; 0 below), [25..34] pcr_fix and
+ *   [35..44] pcr_add as N, v, P (xx xy xz yy yz zz), [45..89] cov_add (upper
+ *   9x9, row-major), [90..92] plane.center, [93..95] normal, [96..116]
+ *   plane_var (upper 6x6), [117] radius, [118..120] eig_value, [121..129]
+ *   eig_vector (row-major), [130] point_fix.size(), then per physical window
+ *   slot: sw->points[s].size(), sw->pcrs_local[s] (N, v, P); zeros without sw.
+ * orc_map_nodes(which 0: the map now, 1: the copy the last step took after
+ * multi_recut, armed by orc_map_dump_after_recut) returns the node count and
+ * info = {nodes, point_fix points, window points, win_count, W, mp[0..W)};
+ * rec is written when cap holds every node. orc_map_points gives the points of
+ * that dump, 12 doubles each (pnt, var row-major): point_fix per node
+ * (fix_off: nodes + 1 offsets) and the window lists per node and physical slot
+ * (body pnt, world var; win_off: nodes * W + 1 offsets). */
+#define ORC_NODE_REC 131
+#define ORC_NODE_SLOT 11
+void orc_map_dump_after_recut(void* h, int on);
+int orc_map_nodes(void* h, int which, double* rec, int cap, long long* info);
+int orc_map_points(void* h, int which, double* fixp, long long* fix_off, double* winp, long long* win_off);
 /* orc_step with IMUEKF::motion_blur's per-point deskew first (imu_ekf.cpp:114-144);
  * times: per-point offset from beg in seconds (the reference's curvature), ascending. */
 int orc_step_deskew(void* h, const float* xyz, const float* inten, const float* times, int n, double beg, double end,

@@ -1019,6 +1019,12 @@ bool host_release_pending(vg_ctx* ctx);  // jour advanced in an absorbed scan si
 // lifetime.hip: the journey release + the node pool / point_fix arena compaction
 int map_release(vg_ctx* ctx, bool release, int thr, double jour, int compact, long long* out);
 int map_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, int* nodes, int* nfix, int cap, int* count);
+// map_dump.cpp (test hook vgx_map_nodes): the map node for
+// node in the oracle's record (oracle/vina_oracle.h ORC_NODE_REC / ORC_NODE_SLOT),
+// assembled on the host from copies of the pool arrays; no device state changes
+constexpr int kNodeRec = 131, kNodeSlot = 11;
+int host_map_nodes(vg_ctx* ctx, double* rec, int cap, double* fixp, long long* fix_off, double* winp,
+                   long long* win_off, long long* info);
 // the root hash rebuilt from (key, id) pairs filed by id, by the bidding rounds (lifetime.hip)
 int map_hash_place(vg_ctx* ctx, int nl, long nroots, const uint64_t* rkey, int* pos, int* rcnt, const char* who);
 // checkpoint.hip / ckpt_host.cpp: the host mirror's part of a checkpoint (a byte

@@ -1140,6 +1140,22 @@ extern "C" int vgx_roots(vg_ctx* ctx, long long* key, double* jour, int* flags, 
   return map_roots(ctx, key, jour, flags, nodes, nfix, cap, n);
 }
 
+// Test-only: the device map node for node (map_dump.cpp), in the record of the
+// oracle's orc_map_nodes / orc_map_points (oracle/vina_oracle.h). Two calls,
+// no state between them: with rec == nullptr, info gives {nodes, point_fix
+// points, window points, win_count, W, mp[0..W)}; with every buffer given, cap
+// == nodes and info[1], info[2] as the count call left them, the records, the
+// point lists (12 doubles each) and their offsets (nodes + 1, nodes * W + 1)
+// are written — VG_E_ARG if the map is no longer the one the count call saw.
+// Callable between scans and, in the stage API, wherever vg_map_planes is.
+// VG_E_STATE on a shared map (owner or attached tracker), a fleet's tracker
+// and a sharded context.
+extern "C" int vgx_map_nodes(vg_ctx* ctx, double* rec, int cap, double* fixp, long long* fix_off, double* winp,
+                             long long* win_off, long long* info) {
+  if (!ctx || !info || cap < 0 || (rec && (!fixp || !fix_off || !winp || !win_off))) return VG_E_ARG;
+  return host_map_nodes(ctx, rec, cap, fixp, fix_off, winp, win_off, info);
+}
+
 // Test-only: the last insert's leaf segments (insert.hip map_insert_segments),
 // read right after vg_cut_voxel_multi: key[s] (leaf id, or a child request
 // -2 - (parent * 8 + octant)), len[s], info[4] = {segments, roots touched,

@@ -56,7 +56,7 @@ def load(name_or_path):
     return out
 
 
-def to_c(p, use_threads=1, vnc_prep=1, scale_gravity=1.0, cold_start=0, release_dis=0):
+def to_c(p, use_threads=1, vnc_prep=1, scale_gravity=1.0, cold_start=0, release_dis=0, max_points=100):
     g, o, b = p["General"], p["Odometry"], p["LocalBA"]
     c = CConfig()
     c.voxel_size = o["voxel_size"]
@@ -74,7 +74,7 @@ def to_c(p, use_threads=1, vnc_prep=1, scale_gravity=1.0, cold_start=0, release_
     for i in range(3):
         c.ext_t[i] = g["extrinsic_tran"][i]
     c.max_layer = b["max_layer"]
-    c.max_points = 100
+    c.max_points = max_points  # octree.cpp:70 (100); the parity tests lower it to reach margi's full-leaf branch
     c.win_size = b["win_size"]
     c.thread_num = b["thread_num"]
     c.if_BA = int(g["if_BA"])

@@ -645,6 +645,9 @@ def lib():
             L.vgx_ba_solve.argtypes = [P, dp, dp, dp]
         if hasattr(L, "vgx_memo_probe"):
             L.vgx_memo_probe.argtypes = [P, ip]
+        if hasattr(L, "vgx_map_nodes"):
+            l64 = ctypes.POINTER(ctypes.c_int64)
+            L.vgx_map_nodes.argtypes = [P, dp, ctypes.c_int, dp, l64, dp, l64, l64]
         if hasattr(L, "vgx_roots"):
             L.vgx_roots.argtypes = [P, ctypes.POINTER(ctypes.c_longlong), dp, ip, ip, ip, ctypes.c_int, ip]
         if hasattr(L, "vgx_la_eval"):
@@ -1477,6 +1480,25 @@ class Context:
         assert m == n, (m, n)
         return {tuple(int(v) for v in key[i]): (float(jour[i]), int(arr[0][i]), int(arr[1][i]), int(arr[2][i]))
                 for i in range(n)}
+
+    def map_nodes(self):
+        """The device map node for node (vgx_map_nodes: a count call, then a data call), as the raw dump of the
+        oracle's Pipeline.map_nodes(): "rec" (one record per node, layout in oracle/vina_oracle.h),
+        "fixp" / "fix_off" (point_fix per node), "winp" / "win_off" (window points per node and
+        physical slot), "win_count", "W" and the ring "mp". Between scans, or inside a stage-level
+        scan wherever map_planes may be called; nothing on the device changes."""
+        lp = ctypes.POINTER(ctypes.c_int64)
+        info = np.zeros(5 + 32, dtype=np.int64)
+        self._chk(lib().vgx_map_nodes(self.h, None, 0, None, None, None, None, info.ctypes.data_as(lp)),
+                  "vgx_map_nodes")
+        n, nf, nw, W = (int(info[i]) for i in (0, 1, 2, 4))
+        rec = np.zeros((max(n, 1), 131 + 11 * W))
+        fixp, winp = np.zeros((max(nf, 1), 12)), np.zeros((max(nw, 1), 12))
+        fix_off, win_off = np.zeros(n + 1, dtype=np.int64), np.zeros(n * W + 1, dtype=np.int64)
+        self._chk(lib().vgx_map_nodes(self.h, _d(rec), n, _d(fixp), fix_off.ctypes.data_as(lp), _d(winp),
+                                      win_off.ctypes.data_as(lp), info.ctypes.data_as(lp)), "vgx_map_nodes")
+        return {"rec": rec[:n], "fixp": fixp[:nf], "winp": winp[:nw], "fix_off": fix_off, "win_off": win_off,
+                "win_count": int(info[3]), "W": W, "mp": [int(v) for v in info[5: 5 + W]]}
 
     def capture_arm(self):
         """Capture the next LM run's first Hessian pass (vgx_debug 5)."""
