@@ -277,28 +277,13 @@ int change_alloc(vg_ctx* ctx, ChangeLayer* L, int hash_log2) {
   d.cap_nodes = ctx->map.cap_nodes > 0 ? ctx->map.cap_nodes : 1;
   const size_t slots = (size_t)1 << hash_log2;
   d.mask = (int)(slots - 1);
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&d.node), (size_t)d.cap_nodes * sizeof(ChangeNode)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&d.ckey), slots * sizeof(unsigned long long)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&d.cell), slots * sizeof(ChangeCell)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&d.tot), 8 * sizeof(long long)));  // kChgTot totals, then the report's scratch
-  L->blk_n = (int)((std::max((size_t)d.cap_nodes, slots) + kBlock - 1) / kBlock);
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&L->d_blk), (size_t)L->blk_n * sizeof(int)));
+  VG_HIP(L->node.reserve((size_t)d.cap_nodes));
+  VG_HIP(L->ckey.reserve(slots));
+  VG_HIP(L->cell.reserve(slots));
+  VG_HIP(L->tot.reserve(8));  // kChgTot totals, then the report's scratch
+  VG_HIP(L->blk.reserve((std::max((size_t)d.cap_nodes, slots) + kBlock - 1) / kBlock));
+  d.node = L->node, d.ckey = L->ckey, d.cell = L->cell, d.tot = L->tot;
   return VG_OK;
-}
-
-void change_free(ChangeLayer* L) {
-  ChangeDev& d = L->d;
-  if (d.node) (void)hipFree(d.node);
-  if (d.ckey) (void)hipFree(d.ckey);
-  if (d.cell) (void)hipFree(d.cell);
-  if (d.tot) (void)hipFree(d.tot);
-  if (L->d_blk) (void)hipFree(L->d_blk);
-  if (L->d_out) (void)hipFree(L->d_out);
-  L->d_blk = nullptr;
-  L->d_out = nullptr;
-  L->blk_n = 0;
-  L->out_bytes = 0;
-  d = ChangeDev();
 }
 
 int change_clear_dev(vg_ctx* ctx, ChangeLayer* L) {
@@ -321,19 +306,19 @@ int change_accum_dev(vg_ctx* ctx, ChangeLayer* L, const MP& mp, const float* x, 
   const DiffPrm q = diff_prm(&L->diff);
   Pose12 pose;
   for (int e = 0; e < 12; e++) pose.v[e] = pose12[e];
-  vg_diff_point* d_pp = per_point ? static_cast<vg_diff_point*>(b.out) : nullptr;
-  vg_diff_summary* d_sum = static_cast<vg_diff_summary*>(b.sum);
+  vg_diff_point* d_pp = per_point ? reinterpret_cast<vg_diff_point*>(b.out.p) : nullptr;
+  vg_diff_summary* d_sum = b.sum;
   if (!dev) {  // the host cloud, n x 3, into the staging vg_scan_diff uses
-    float* d_xyz = reinterpret_cast<float*>(b.dir);
+    float* d_xyz = reinterpret_cast<float*>(b.dir.p);
     VG_HIP(hipMemcpyAsync(d_xyz, x, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
     x = d_xyz, y = d_xyz + 1, z = d_xyz + 2;
   }
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_diff_summary), s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   k_change_accum<<<(n + kRayBlock - 1) / kRayBlock, kRayBlock, 0, s>>>(mp, ctx->map, L->d, x, y, z, stride, n, pose, q,
                                                                       epoch, d_pp, b.org, reinterpret_cast<int*>(d_sum));
   diff_sum_launch(s, b.org, n, d_sum);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_diff_summary), hipMemcpyDeviceToHost, s));
   if (per_point) VG_HIP(hipMemcpyAsync(per_point, d_pp, (size_t)n * sizeof(vg_diff_point), hipMemcpyDeviceToHost, s));
@@ -349,11 +334,11 @@ static int change_pass(vg_ctx* ctx, ChangeLayer* L, const ChangeQ& q, int n, std
   const int nb = (n + kBlock - 1) / kBlock;
   out.clear();
   if (nb == 0) return VG_OK;
-  if (nb > L->blk_n) {
+  if ((size_t)nb > L->blk.cap) {
     ctx->err = "vg_change_report: more items than the layer's scratch was sized for";
     return VG_E_STATE;
   }
-  int* d_blk = L->d_blk;
+  int* d_blk = L->blk;
   k_change_count<KIND><<<nb, kBlock, 0, s>>>(L->d, q, n, d_blk, agg);
   VG_HIP(hipGetLastError());
   k_change_scan<<<1, kBlock, 0, s>>>(d_blk, nb, agg + 2);
@@ -363,15 +348,9 @@ static int change_pass(vg_ctx* ctx, ChangeLayer* L, const ChangeQ& q, int n, std
   VG_HIP(hipStreamSynchronize(s));
   if (total == 0) return VG_OK;
   const size_t bytes = (size_t)total * sizeof(Rec);
-  if (bytes > L->out_bytes) {  // the record staging, kept in the layer and grown geometrically
-    if (L->d_out) (void)hipFree(L->d_out);
-    L->d_out = nullptr;
-    L->out_bytes = 0;
-    const size_t want = std::max(bytes, (size_t)1 << 16) * 2;
-    VG_HIP(hipMalloc(&L->d_out, want));
-    L->out_bytes = want;
-  }
-  Rec* d_out = static_cast<Rec*>(L->d_out);
+  // the record staging, kept in the layer and grown geometrically
+  if (bytes > L->out.cap) VG_HIP(L->out.reserve(std::max(bytes, (size_t)1 << 16) * 2));
+  Rec* d_out = reinterpret_cast<Rec*>(L->out.p);
   k_change_emit<KIND, Rec><<<nb, kBlock, 0, s>>>(ctx->map, L->d, q, n, d_blk, d_out, (int)total);
   VG_HIP(hipGetLastError());
   out.resize((size_t)total);

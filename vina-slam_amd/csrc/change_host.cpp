@@ -37,7 +37,6 @@ int host_change_begin(vg_ctx* ctx, const vg_change_params* prm) {
   int r = change_alloc(ctx, L, log2);
   if (r == VG_OK) r = change_clear_dev(ctx, L);
   if (r != VG_OK) {
-    change_free(L);
     delete L;
     return r;
   }
@@ -136,7 +135,6 @@ int host_change_end(vg_ctx* ctx) {
   std::lock_guard<std::mutex> lock(ctx->change_mu);
   VG_TRY(owner_layer(ctx, "vg_change_end", &L));
   ctx->change = nullptr;
-  change_free(L);
   delete L;
   return VG_OK;
 }

@@ -199,16 +199,16 @@ __global__ void __launch_bounds__(256) k_ckpt_runs_pack(DevMap m, int n, const i
   }
 }
 
-struct DevBuf {  // a device (or pinned host) allocation freed at scope exit
+struct PinBuf {  // a pinned host allocation freed at scope exit
   void* p = nullptr;
-  bool host = false;
-  ~DevBuf() {
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
   }
 };
+using Scratch = DevBuf<char>;  // device scratch of one call, in bytes
 #define CK_ALLOC(buf, bytes, what)                                                                         \
   do {                                                                                                     \
-    const hipError_t e_ = hipMalloc(&(buf).p, (bytes) > 0 ? (size_t)(bytes) : 64);                         \
+    const hipError_t e_ = (buf).reserve((bytes) > 0 ? (size_t)(bytes) : 64);                               \
     if (e_ != hipSuccess) {                                                                                \
       ctx->err = std::string(who) + ": " + what + " (" + std::to_string((size_t)(bytes) >> 20) + " MiB): " + \
                  hipGetErrorString(e_);                                                                    \
@@ -335,7 +335,7 @@ void build_layout(vg_ctx* ctx, const CkptDims& d, uint64_t host_bytes, char* img
 
 int run_copy(vg_ctx* ctx, const Layout& L, const char* who) {
   if (L.copy.empty()) return VG_OK;
-  DevBuf dd;
+  Scratch dd;
   CK_ALLOC(dd, L.copy.size() * sizeof(CopyDesc), "descriptor list");
   VG_HIP(hipMemcpyAsync(dd.p, L.copy.data(), L.copy.size() * sizeof(CopyDesc), hipMemcpyHostToDevice, ctx->stream));
   k_ckpt_copy<<<dim3(kCopyX, (unsigned)L.copy.size()), kBlock, 0, ctx->stream>>>((const CopyDesc*)dd.p);
@@ -352,7 +352,7 @@ int run_sums(vg_ctx* ctx, const unsigned char* img, const std::vector<CkptSec>& 
     sd[i].off = sec[i].off;
     sd[i].words = (sec[i].bytes + 7) / 8;
   }
-  DevBuf b;
+  Scratch b;
   const size_t o_part = (ns * sizeof(SumDesc) + 255) & ~size_t(255), o_out = o_part + ns * kSumX * 8;
   CK_ALLOC(b, o_out + ns * 8, "checksum scratch");
   char* p = (char*)b.p;
@@ -403,7 +403,7 @@ int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_m
   for (int k = d.W; k < 32; k++) d.wpn[k] = d.arena[k] = 0;
   // the root pairs, appended in any order, then ordered by id
   const size_t un = (size_t)(d.n_nodes > 0 ? d.n_nodes : 1);
-  DevBuf rb;
+  Scratch rb;
   const size_t o_ids = 256, o_keys = (o_ids + un * 4 + 255) & ~size_t(255), o_end = o_keys + un * 8;
   CK_ALLOC(rb, o_end, "root scratch");
   char* rp = (char*)rb.p;
@@ -419,7 +419,7 @@ int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_m
   }
   // the leaf runs' canonical places (k_ckpt_runs_count): one scan over (slot, region, node)
   const size_t cells = (size_t)2 * d.W * un + 1;
-  DevBuf runs;
+  Scratch runs;
   size_t scan_tb = 0;
   VG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tb, (int*)nullptr, (int*)nullptr, (int)cells, s));
   const size_t o_off = (cells * 4 + 255) & ~size_t(255), o_tmp = o_off + ((cells * 4 + 255) & ~size_t(255));
@@ -447,7 +447,7 @@ int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_m
   host_ckpt_blob(ctx, blob);
   Layout L;
   build_layout(ctx, d, blob.size(), nullptr, true, L);  // sizes first
-  DevBuf img;
+  Scratch img;
   CK_ALLOC(img, L.image_bytes, "image");
   L = Layout();
   build_layout(ctx, d, blob.size(), (char*)img.p, true, L);
@@ -476,7 +476,7 @@ int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_m
     while ((1L << end_bit) <= (long)d.n_nodes) end_bit++;
     VG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint64_t*)nullptr,
                                               (uint64_t*)nullptr, d.n_roots, 0, end_bit, s));
-    DevBuf tmp;
+    Scratch tmp;
     CK_ALLOC(tmp, tb, "sort scratch");
     VG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, (const uint32_t*)(rp + o_ids), (uint32_t*)((char*)img.p + s_id->off),
                                               (const uint64_t*)(rp + o_keys), (uint64_t*)((char*)img.p + s_key->off),
@@ -493,8 +493,7 @@ int checkpoint_save(vg_ctx* ctx, const char* path, long long* bytes, double* t_m
   // header + image in one pinned buffer, one D2H copy
   const uint32_t nsec = (uint32_t)L.sec.size();
   const uint64_t hb = ckpt_head_bytes(nsec), total = hb + L.image_bytes;
-  DevBuf pin;
-  pin.host = true;
+  PinBuf pin;
   {
     const hipError_t e = hipHostMalloc(&pin.p, total, hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -553,8 +552,7 @@ int checkpoint_load(vg_ctx* ctx, const char* path, double* t_ms) {
   fseek(fp, 0, SEEK_END);
   const long flen = ftell(fp);
   fseek(fp, 0, SEEK_SET);
-  DevBuf pin;
-  pin.host = true;
+  PinBuf pin;
   if (flen > 0 && hipHostMalloc(&pin.p, (size_t)flen, hipHostMallocDefault) != hipSuccess) {
     pin.p = nullptr;
     fclose(fp);
@@ -586,7 +584,7 @@ int checkpoint_load(vg_ctx* ctx, const char* path, double* t_ms) {
   t0 = now_ms();
   // 4: the checksums, recomputed on the device over the uploaded image
   hipStream_t s = ctx->stream;
-  DevBuf img;
+  Scratch img;
   CK_ALLOC(img, v.head.image_bytes, "image");
   if (v.head.image_bytes > 0)
     VG_HIP(hipMemcpyAsync(img.p, f + v.head.head_bytes, v.head.image_bytes, hipMemcpyHostToDevice, s));
@@ -649,12 +647,11 @@ int checkpoint_load(vg_ctx* ctx, const char* path, double* t_ms) {
   // the root hash, rebuilt for this context's table size
   if (d.n_nodes > 0) {
     const size_t un = (size_t)d.n_nodes;
-    DevBuf hb;
+    Scratch hb;
     const size_t o_pos = (un * 8 + 255) & ~size_t(255), o_cnt = (o_pos + un * 4 + 255) & ~size_t(255);
     {
-      const hipError_t e2 = hipMalloc(&hb.p, o_cnt + 256);
+      const hipError_t e2 = hb.reserve(o_cnt + 256);
       if (e2 != hipSuccess) {
-        hb.p = nullptr;
         ctx->err = std::string(who) + ": hash scratch: " + hipGetErrorString(e2);
         return fail(VG_E_HIP);
       }

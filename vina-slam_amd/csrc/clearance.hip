@@ -159,42 +159,18 @@ __global__ void __launch_bounds__(kClrBlock) k_clr_rows(const int8_t* __restrict
 static int clr_bufs(vg_ctx* ctx, size_t cells, bool want_dist2, bool want_nearest, bool want_cost) {
   ClrBufs& b = ctx->clr;
   static_assert(sizeof(vg_clr_params) == 80 && sizeof(vg_clr_summary) == 128, "the records' documented sizes");
-  if (!b.ready) {
-    VG_HIP(hipMalloc(&b.sum, sizeof(vg_clr_summary)));
-    for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-    b.ready = true;
-  }
-  if (cells > b.cells) {
-    if (b.grid) (void)hipFree(b.grid);
-    if (b.dy) (void)hipFree(b.dy);
-    if (b.dist2) (void)hipFree(b.dist2);
-    if (b.nearest) (void)hipFree(b.nearest);
-    if (b.cost) (void)hipFree(b.cost);
-    b.grid = nullptr, b.dy = nullptr, b.dist2 = nullptr, b.nearest = nullptr, b.cost = nullptr;
-    b.cells = 0;
+  VG_HIP(b.sum.reserve(1));
+  bool regrown = false;
+  VG_HIP(b.grid.reserve(cells, &regrown));
+  if (regrown) {  // the other planes go with it; an output comes back at the new capacity once a call asks for it
+    b.dy.release(), b.dist2.release(), b.nearest.release(), b.cost.release();
     b.nx = b.ny = 0;
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.grid), cells));
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dy), cells * sizeof(int16_t)));
-    b.cells = cells;
   }
-  if (want_dist2 && !b.dist2) VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dist2), b.cells * sizeof(int)));
-  if (want_nearest && !b.nearest) VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.nearest), b.cells * sizeof(int)));
-  if (want_cost && !b.cost) VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.cost), b.cells));
+  VG_HIP(b.dy.reserve(b.grid.cap));
+  if (want_dist2) VG_HIP(b.dist2.reserve(b.grid.cap));
+  if (want_nearest) VG_HIP(b.nearest.reserve(b.grid.cap));
+  if (want_cost) VG_HIP(b.cost.reserve(b.grid.cap));
   return VG_OK;
-}
-
-void clr_free(vg_ctx* ctx) {
-  ClrBufs& b = ctx->clr;
-  if (b.grid) (void)hipFree(b.grid);
-  if (b.dy) (void)hipFree(b.dy);
-  if (b.dist2) (void)hipFree(b.dist2);
-  if (b.nearest) (void)hipFree(b.nearest);
-  if (b.cost) (void)hipFree(b.cost);
-  if (b.table) (void)hipFree(b.table);
-  if (b.sum) (void)hipFree(b.sum);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = ClrBufs();
 }
 
 // the cost table on the device is the one these parameters give: kept while they stay
@@ -211,20 +187,14 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
   VG_TRY(clr_bufs(ctx, cells, dist2 != nullptr, nearest != nullptr, cost != nullptr));
   ClrBufs& b = ctx->clr;
   hipStream_t s = ctx->stream;
-  unsigned long long* d_sum = static_cast<unsigned long long*>(b.sum);
-  const int8_t* d_grid = grid ? b.grid : ctx->occ.grid;
-  b.ms = 0.0;
+  unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
+  const int8_t* d_grid = grid ? b.grid.p : ctx->occ.grid.p;
+  b.t.clear();
   if (cost) b.nx = b.ny = 0;  // (no cost plane to hand to vg_navfn until this call has finished)
   if (table) {
     const double key[4] = {prm->res, prm->inscribed_radius, prm->inflation_radius, prm->cost_scaling};
     b.table_n = 0;
-    if ((size_t)table_n > b.table_cap) {
-      if (b.table) (void)hipFree(b.table);
-      b.table = nullptr;
-      b.table_cap = 0;
-      VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.table), (size_t)table_n));
-      b.table_cap = (size_t)table_n;
-    }
+    VG_HIP(b.table.reserve((size_t)table_n));
     VG_HIP(hipMemcpyAsync(b.table, table, (size_t)table_n, hipMemcpyHostToDevice, s));
     VG_HIP(hipStreamSynchronize(s));  // (the caller's table goes away with the call)
     memcpy(b.table_key, key, sizeof(key));
@@ -232,23 +202,21 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
   }
   if (grid) VG_HIP(hipMemcpyAsync(b.grid, grid, cells, hipMemcpyHostToDevice, s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_clr_summary), s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   k_clr_cols<<<(nx + kClrBlock - 1) / kClrBlock, kClrBlock, 0, s>>>(d_grid, nx, ny, prm->flags & 1, b.dy, d_sum);
   VG_HIP(hipGetLastError());
   k_clr_rows<<<ny, kClrBlock, (size_t)nx * sizeof(int16_t), s>>>(d_grid, b.dy, nx, b.table, table_n,
-                                                                   dist2 ? b.dist2 : nullptr,
-                                                                   nearest ? b.nearest : nullptr,
-                                                                   cost ? b.cost : nullptr, d_sum);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+                                                                   dist2 ? b.dist2.p : nullptr,
+                                                                   nearest ? b.nearest.p : nullptr,
+                                                                   cost ? b.cost.p : nullptr, d_sum);
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   if (dist2) VG_HIP(hipMemcpyAsync(dist2, b.dist2, cells * sizeof(int), hipMemcpyDeviceToHost, s));
   if (nearest) VG_HIP(hipMemcpyAsync(nearest, b.nearest, cells * sizeof(int), hipMemcpyDeviceToHost, s));
   if (cost) VG_HIP(hipMemcpyAsync(cost, b.cost, cells, hipMemcpyDeviceToHost, s));
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_clr_summary), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
-  b.ms = t;
+  VG_HIP(b.t.collect());
   if (cost) b.nx = nx, b.ny = ny;
   return VG_OK;
 }
@@ -258,7 +226,7 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
 // Measurement hook: the device time of the last vg_clearance call's two kernels (HIP events on the context
 // stream around them)
 extern "C" int vgx_clr_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->clr.ev[0]) return VG_E_ARG;
-  *ms = ctx->clr.ms;
+  if (!ctx || !ms || !ctx->clr.t.armed()) return VG_E_ARG;
+  *ms = ctx->clr.t.ms;
   return VG_OK;
 }

@@ -37,8 +37,8 @@ struct vg_fleet {
   std::vector<char> split;        // its IEKF overlap / downsample stream settings (vg_multi_create's bits)
   vg::FleetIn* h_in = nullptr;    // kRing x B blocks, host-mapped
   vg::FleetIn* d_in = nullptr;
-  vg::FleetTab* d_tab = nullptr;  // B entries, device
-  int* d_act = nullptr;           // B active flags, device
+  vg::DevBuf<vg::FleetTab> d_tab;  // B entries, device
+  vg::DevBuf<int> d_act;           // B active flags, device
   SlotUse use[kRing];
   long step = 0;
   int nb = 0;                     // the IEKF grid per tracker
@@ -95,8 +95,7 @@ int vg_fleet_create(vg_ctx* owner, vg_ctx** trackers, int B, vg_fleet** out) {
       (e = hipHostGetDevicePointer((void**)&f->d_in, f->h_in, 0)) != hipSuccess)
     return fail(e);
   memset(f->h_in, 0, in_bytes);
-  if ((e = hipMalloc((void**)&f->d_tab, B * sizeof(FleetTab))) != hipSuccess ||
-      (e = hipMalloc((void**)&f->d_act, B * sizeof(int))) != hipSuccess ||
+  if ((e = f->d_tab.reserve(B)) != hipSuccess || (e = f->d_act.reserve(B)) != hipSuccess ||
       (e = hipMemset(f->d_act, 0, B * sizeof(int))) != hipSuccess)
     return fail(e);
   std::vector<FleetTab> tab(B);
@@ -252,8 +251,6 @@ void vg_fleet_destroy(vg_fleet* f) {
     if (f->split[b] & 1) c->overlap_iekf = true;
     c->fleet = nullptr;
   }
-  if (f->d_tab) (void)hipFree(f->d_tab);
-  if (f->d_act) (void)hipFree(f->d_act);
   if (f->h_in) (void)hipHostFree(f->h_in);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;

@@ -101,20 +101,18 @@ extern "C" int vgx_la_eval(vg_ctx* ctx, int op, const double* in, int in_stride,
   if (in_stride < kLaIn[op] || out_stride < kLaOut[op] || in_stride > 1024 || out_stride > 1024) return VG_E_ARG;
   VG_TRY(host_sync(ctx));
   const size_t nin = (size_t)n * in_stride * sizeof(double), nout = (size_t)n * out_stride * sizeof(double);
-  double *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc((void**)&d_in, nin);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, nout);
+  DevBuf<double> d_in, d_out;
+  hipError_t e = d_in.reserve((size_t)n * in_stride);
+  if (e == hipSuccess) e = d_out.reserve((size_t)n * out_stride);
   if (e == hipSuccess) e = hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(d_out, 0, nout);
   if (e == hipSuccess) e = hipDeviceSynchronize();  // (the context's stream does not wait for the null stream)
   if (e == hipSuccess) {
-    la_launch<0>(op, ctx->stream, d_in, in_stride, d_out, out_stride, n);
+    la_launch<0>(op, ctx->stream, d_in.p, in_stride, d_out.p, out_stride, n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
   if (e != hipSuccess) {
     ctx->err = std::string("vgx_la_eval: ") + hipGetErrorString(e);
     return VG_E_HIP;

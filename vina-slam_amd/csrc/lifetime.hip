@@ -219,14 +219,15 @@ __global__ void __launch_bounds__(256) k_roots_rows(DevMap m, int n, const int* 
 
 template <class F>
 int with_scratch(vg_ctx* ctx, size_t bytes, void** p, F&& body) {
-  const hipError_t e = hipMalloc(p, bytes > 0 ? bytes : 64);
+  DevBuf<char> buf;
+  const hipError_t e = buf.reserve(bytes > 0 ? bytes : 64);
   if (e != hipSuccess) {
     ctx->err = std::string("vg_release_far: scratch (") + std::to_string(bytes >> 20) + " MiB): " + hipGetErrorString(e);
     return VG_E_HIP;
   }
+  *p = buf.p;
   const int r = body();
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(*p);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // (buf is freed at the return, after the drain)
   if (r != VG_OK) return r;
   if (e2 != hipSuccess) {
     ctx->err = std::string("vg_release_far: ") + hipGetErrorString(e2);

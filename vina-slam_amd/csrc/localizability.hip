@@ -133,38 +133,14 @@ __global__ void __launch_bounds__(64) k_info_scan_sum(const InfoPart* __restrict
 
 static int info_bufs(vg_ctx* ctx) {
   InfoBufs& b = ctx->info;
-  if (b.slab > 0) return VG_OK;
   static_assert(sizeof(vg_info_rec) == 416 && sizeof(vg_info_params) == 112 && sizeof(InfoPart) == 184,
                 "the records' documented sizes");
   const size_t slab = (size_t)(b.slab_want > 0 ? b.slab_want : kInfoSlab);
   const size_t pts = (size_t)(ctx->cap.max_points_per_scan > 0 ? ctx->cap.max_points_per_scan : 1);
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.pos), slab * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dirs), (size_t)kInfoMaxDirs * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(&b.out, slab * sizeof(vg_info_rec)));
-  VG_HIP(hipMalloc(&b.part, ((pts + kInfoBlock - 1) / kInfoBlock) * sizeof(InfoPart)));
-  for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-  b.slab = (int)slab;
-  return VG_OK;
-}
-
-void info_free(vg_ctx* ctx) {
-  InfoBufs& b = ctx->info;
-  if (b.pos) (void)hipFree(b.pos);
-  if (b.dirs) (void)hipFree(b.dirs);
-  if (b.out) (void)hipFree(b.out);
-  if (b.part) (void)hipFree(b.part);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  const int want = b.slab_want;
-  b = InfoBufs();
-  b.slab_want = want;
-}
-
-static int info_elapsed(vg_ctx* ctx) {
-  InfoBufs& b = ctx->info;
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
-  b.ms += t;
+  VG_HIP(b.pos.reserve(slab * 3));
+  VG_HIP(b.dirs.reserve((size_t)kInfoMaxDirs * 3));
+  VG_HIP(b.out.reserve(slab));
+  VG_HIP(b.part.reserve((pts + kInfoBlock - 1) / kInfoBlock));
   return VG_OK;
 }
 
@@ -175,20 +151,21 @@ int localizability_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M
   InfoBufs& b = ctx->info;
   hipStream_t s = ctx->stream;
   const InfoPrm q = info_prm(prm);
-  vg_info_rec* d_out = static_cast<vg_info_rec*>(b.out);
-  b.ms = 0.0;
+  vg_info_rec* d_out = b.out;
+  const int slab = (int)b.out.cap;
+  b.t.clear();
   VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-  for (int i0 = 0; i0 < M; i0 += b.slab) {
-    const int m = M - i0 < b.slab ? M - i0 : b.slab;
+  for (int i0 = 0; i0 < M; i0 += slab) {
+    const int m = M - i0 < slab ? M - i0 : slab;
     VG_HIP(hipMemcpyAsync(b.pos, positions + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VG_HIP(hipEventRecord(b.ev[0], s));
+    VG_HIP(b.t.begin(s));
     k_info_places<<<m, kInfoBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, q, (double)mp.dept * (double)mp.dept,
                                            mp.beam_dv, d_out);
-    VG_HIP(hipEventRecord(b.ev[1], s));
+    VG_HIP(b.t.end(s));
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(out + i0, d_out, (size_t)m * sizeof(vg_info_rec), hipMemcpyDeviceToHost, s));
     VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
-    VG_TRY(info_elapsed(ctx));
+    VG_HIP(b.t.collect());
   }
   return VG_OK;
 }
@@ -205,20 +182,21 @@ int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
   const InfoPrm q = info_prm(prm);
   Pose12 pose;
   for (int e = 0; e < 12; e++) pose.v[e] = pose12[e];
-  float* d_xyz = reinterpret_cast<float*>(ctx->ray.dir);  // (the cloud's staging of vg_scan_diff: n <= its capacity)
-  InfoPart* d_part = static_cast<InfoPart*>(b.part);
-  vg_info_rec* d_out = static_cast<vg_info_rec*>(b.out);
+  float* d_xyz = reinterpret_cast<float*>(ctx->ray.dir.p);  // (the cloud's staging of vg_scan_diff: n <= its capacity)
+  InfoPart* d_part = b.part;
+  vg_info_rec* d_out = b.out;
   const int n_blocks = (n + kInfoBlock - 1) / kInfoBlock;
-  b.ms = 0.0;
+  b.t.clear();
   VG_HIP(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   k_info_scan<<<n_blocks, kInfoBlock, 0, s>>>(mp, ctx->map, d_xyz, n, pose, dq, q.floor_var, d_part);
   k_info_scan_sum<<<1, 64, 0, s>>>(d_part, n_blocks, n, q.min_hits, d_out);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(out, d_out, sizeof(vg_info_rec), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
-  return info_elapsed(ctx);
+  VG_HIP(b.t.collect());
+  return VG_OK;
 }
 
 }  // namespace vg
@@ -228,14 +206,18 @@ int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
 // vgx_info_slab: the places per launch of vg_localizability from the next call on (<= 0: the default); the
 // staging is freed and allocated again at that size
 extern "C" int vgx_info_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->info.ev[0]) return VG_E_ARG;
-  *ms = ctx->info.ms;
+  if (!ctx || !ms || !ctx->info.t.armed()) return VG_E_ARG;
+  *ms = ctx->info.t.ms;
   return VG_OK;
 }
 extern "C" int vgx_info_slab(vg_ctx* ctx, int places) {
   if (!ctx) return VG_E_ARG;
   if (ctx->stream) VG_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->info.slab_want = places > 0 ? places : 0;
-  vg::info_free(ctx);
+  vg::InfoBufs& b = ctx->info;
+  b.slab_want = places > 0 ? places : 0;
+  b.pos.release();
+  b.dirs.release();
+  b.out.release();
+  b.part.release();
   return VG_OK;
 }

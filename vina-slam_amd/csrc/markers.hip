@@ -278,13 +278,6 @@ static int used_nodes(vg_ctx* ctx, int* n) {
   return VG_OK;
 }
 
-void markers_free(vg_ctx* ctx) {
-  if (ctx->d_mk) (void)hipFree(ctx->d_mk);
-  if (ctx->d_mk_cnt) (void)hipFree(ctx->d_mk_cnt);
-  ctx->d_mk = nullptr;
-  ctx->d_mk_cnt = nullptr;
-}
-
 // the caller has completed the outstanding work (vg_set_publish)
 int markers_enable(vg_ctx* ctx, bool on) {
   if (on && ctx->cfg.max_layer >= kMkDepth) {
@@ -299,11 +292,12 @@ int markers_enable(vg_ctx* ctx, bool on) {
   if (n > 0 && !keep) k_mk_clear<<<grid_for(n), kBlock, 0, ctx->stream>>>(ctx->map, n);
   VG_HIP(hipGetLastError());
   VG_HIP(hipStreamSynchronize(ctx->stream));
-  markers_free(ctx);
+  ctx->d_mk.release();
+  ctx->d_mk_cnt.release();
   ctx->mk_fresh = false;
   if (!on) return VG_OK;
-  VG_HIP(hipMalloc((void**)&ctx->d_mk, (size_t)ctx->mk_cap * sizeof(vg_plane_marker)));
-  VG_HIP(hipMalloc((void**)&ctx->d_mk_cnt, 4 * sizeof(int)));
+  VG_HIP(ctx->d_mk.reserve((size_t)ctx->mk_cap));
+  VG_HIP(ctx->d_mk_cnt.reserve(4));
   VG_HIP(hipMemset(ctx->d_mk_cnt, 0, 4 * sizeof(int)));
   return VG_OK;
 }
@@ -339,21 +333,20 @@ int map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n) {
   int nn = 0;
   VG_TRY(used_nodes(ctx, &nn));
   const int k = out ? cap : 0;
-  char* buf = nullptr;  // the count, then the records
+  DevBuf<char> buf;  // the count, then the records
   const size_t off = 256;
-  hipError_t e = hipMalloc((void**)&buf, off + (size_t)(k > 0 ? k : 1) * sizeof(vg_plane_marker));
+  hipError_t e = buf.reserve(off + (size_t)(k > 0 ? k : 1) * sizeof(vg_plane_marker));
   if (e == hipSuccess) e = hipMemsetAsync(buf, 0, off, s);
   int total = 0;
   if (e == hipSuccess) {
     k_mk_snapshot<<<grid_for((long)ctx->map.hash_mask + 1, kBlock, 2048), kBlock, 0, s>>>(
-        ctx->map, nn, ctx->cfg.max_layer, flags, k > 0 ? (vg_plane_marker*)(buf + off) : nullptr, k, (int*)buf);
+        ctx->map, nn, ctx->cfg.max_layer, flags, k > 0 ? (vg_plane_marker*)(buf + off) : nullptr, k, (int*)buf.p);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(&total, buf, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   const int c = total < k ? total : k;
   if (e == hipSuccess && c > 0) e = hipMemcpy(out, buf + off, (size_t)c * sizeof(vg_plane_marker), hipMemcpyDeviceToHost);
-  if (buf) (void)hipFree(buf);
   if (e != hipSuccess) {
     ctx->err = std::string("vg_map_planes: ") + hipGetErrorString(e);
     return VG_E_HIP;
@@ -372,10 +365,10 @@ extern "C" int vgx_marker_eval(vg_ctx* ctx, const double* in, int n, vg_plane_ma
   if (!ctx || !in || !out || n <= 0 || n > (1 << 20)) return VG_E_ARG;
   VG_TRY(host_sync(ctx));
   const size_t nin = (size_t)n * kMkEvalIn * sizeof(double), nout = (size_t)n * sizeof(vg_plane_marker);
-  double* d_in = nullptr;
-  vg_plane_marker* d_out = nullptr;
-  hipError_t e = hipMalloc((void**)&d_in, nin);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, nout);
+  DevBuf<double> d_in;
+  DevBuf<vg_plane_marker> d_out;
+  hipError_t e = d_in.reserve((size_t)n * kMkEvalIn);
+  if (e == hipSuccess) e = d_out.reserve((size_t)n);
   if (e == hipSuccess) e = hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();  // (the context's stream does not wait for the null stream)
   if (e == hipSuccess) {
@@ -384,8 +377,6 @@ extern "C" int vgx_marker_eval(vg_ctx* ctx, const double* in, int n, vg_plane_ma
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
   if (e != hipSuccess) {
     ctx->err = std::string("vgx_marker_eval: ") + hipGetErrorString(e);
     return VG_E_HIP;

@@ -287,54 +287,21 @@ __global__ void __launch_bounds__(kNavBlock) k_nav_descend(const uint16_t* __res
 
 // ---- host side
 
-static int nav_ready(vg_ctx* ctx) {
-  NavBufs& b = ctx->nav;
-  static_assert(sizeof(vg_nav_params) == 64 && sizeof(vg_nav_summary) == 128, "the records' documented sizes");
-  if (b.ready) return VG_OK;
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.table), 256 * sizeof(uint16_t)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.goals), 2 * (size_t)kNavMaxPoints * sizeof(int)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.marks), kNavBatchMax * sizeof(unsigned)));
-  VG_HIP(hipMalloc(&b.sum, sizeof(vg_nav_summary)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.len), (size_t)kNavMaxPoints * sizeof(int)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.status), (size_t)kNavMaxPoints * sizeof(int)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.path_cost), (size_t)kNavMaxPoints * sizeof(long long)));
-  for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-  b.ready = true;
-  return VG_OK;
-}
-
 static int nav_bufs(vg_ctx* ctx, size_t cells, size_t tiles) {
   NavBufs& b = ctx->nav;
-  VG_TRY(nav_ready(ctx));
-  if (cells > b.cells) {
-    if (b.cost) (void)hipFree(b.cost);
-    if (b.trav) (void)hipFree(b.trav);
-    if (b.pot) (void)hipFree(b.pot);
-    b.cost = nullptr, b.trav = nullptr, b.pot = nullptr;
-    b.cells = 0;
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.cost), cells));
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.trav), cells * sizeof(uint16_t)));
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.pot), cells * sizeof(unsigned)));
-    b.cells = cells;
-  }
-  if (tiles > b.act_cap) {
-    if (b.act) (void)hipFree(b.act);
-    b.act = nullptr;
-    b.act_cap = 0;
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.act), 2 * tiles * sizeof(int)));
-    b.act_cap = tiles;
-  }
+  static_assert(sizeof(vg_nav_params) == 64 && sizeof(vg_nav_summary) == 128, "the records' documented sizes");
+  VG_HIP(b.table.reserve(256));
+  VG_HIP(b.goals.reserve(2 * (size_t)kNavMaxPoints));
+  VG_HIP(b.marks.reserve(kNavBatchMax));
+  VG_HIP(b.sum.reserve(1));
+  VG_HIP(b.len.reserve(kNavMaxPoints));
+  VG_HIP(b.status.reserve(kNavMaxPoints));
+  VG_HIP(b.path_cost.reserve(kNavMaxPoints));
+  VG_HIP(b.cost.reserve(cells));
+  VG_HIP(b.trav.reserve(cells));
+  VG_HIP(b.pot.reserve(cells));
+  VG_HIP(b.act.reserve(2 * tiles));
   return VG_OK;
-}
-
-void nav_free(vg_ctx* ctx) {
-  NavBufs& b = ctx->nav;
-  void* all[] = {b.cost, b.trav, b.pot, b.act, b.table, b.goals, b.marks, b.sum, b.cells_out, b.len, b.status, b.path_cost};
-  for (void* p : all)
-    if (p) (void)hipFree(p);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = NavBufs();
 }
 
 int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const uint16_t* table, const int32_t* goals,
@@ -347,16 +314,16 @@ int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const 
   b.nx = b.ny = 0;  // (no field for vg_nav_paths until this call has finished)
   VG_TRY(nav_bufs(ctx, cells, tiles));
   hipStream_t s = ctx->stream;
-  unsigned long long* d_sum = static_cast<unsigned long long*>(b.sum);
-  const uint8_t* d_cost = cost ? b.cost : ctx->clr.cost;
+  unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
+  const uint8_t* d_cost = cost ? b.cost.p : ctx->clr.cost.p;
   int* act[2] = {b.act, b.act + tiles};
-  b.ms = 0.0;
+  b.t.clear();
   VG_HIP(hipMemcpyAsync(b.table, table, 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
   VG_HIP(hipMemcpyAsync(b.goals, goals, 2 * (size_t)n_goals * sizeof(int), hipMemcpyHostToDevice, s));
   if (cost) VG_HIP(hipMemcpyAsync(b.cost, cost, cells, hipMemcpyHostToDevice, s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_nav_summary), s));
   VG_HIP(hipMemsetAsync(b.act, 0, 2 * tiles * sizeof(int), s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   VG_HIP(hipMemsetAsync(b.pot, 0xFF, cells * sizeof(unsigned), s));  // kNavUnreached everywhere
   const size_t lanes = cells > (size_t)n_goals ? cells : (size_t)n_goals;
   k_nav_init<<<(unsigned)((lanes + kNavBlock - 1) / kNavBlock), kNavBlock, 0, s>>>(d_cost, b.table, nx, ny, b.goals, n_goals,
@@ -385,15 +352,13 @@ int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const 
   }
   const size_t blocks = (cells + kNavBlock - 1) / kNavBlock;
   k_nav_sum<<<(unsigned)(blocks < 2048 ? blocks : 2048), kNavBlock, 0, s>>>(b.pot, cells, d_sum);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   if (pot) VG_HIP(hipMemcpyAsync(pot, b.pot, cells * sizeof(unsigned), hipMemcpyDeviceToHost, s));
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_nav_summary), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
   out->rounds = rounds;
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
-  b.ms = t;
+  VG_HIP(b.t.collect());
   b.nx = nx, b.ny = ny;
   return VG_OK;
 }
@@ -403,21 +368,15 @@ int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len,
   NavBufs& b = ctx->nav;
   hipStream_t s = ctx->stream;
   const size_t n_out = (size_t)n_starts * (size_t)max_len;
-  if (n_out > b.cells_out_cap) {
-    if (b.cells_out) (void)hipFree(b.cells_out);
-    b.cells_out = nullptr;
-    b.cells_out_cap = 0;
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.cells_out), n_out * sizeof(int)));
-    b.cells_out_cap = n_out;
-  }
-  b.ms = 0.0;
+  VG_HIP(b.cells_out.reserve(n_out));
+  b.t.clear();
   VG_HIP(hipMemcpyAsync(b.goals, starts, 2 * (size_t)n_starts * sizeof(int), hipMemcpyHostToDevice, s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   VG_HIP(hipMemsetAsync(b.cells_out, 0xFF, n_out * sizeof(int), s));  // -1 past a path's end
   k_nav_descend<<<(n_starts + kNavBlock - 1) / kNavBlock, kNavBlock, 0, s>>>(b.trav, b.pot, b.nx, b.ny, b.goals, n_starts,
                                                                             max_len, b.cells_out, b.len, b.status,
                                                                             b.path_cost);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   // (into the caller's arrays only once the kernel ran: a failed launch writes nothing)
   VG_HIP(hipMemcpyAsync(cells, b.cells_out, n_out * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -426,9 +385,7 @@ int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len,
   if (path_cost)
     VG_HIP(hipMemcpyAsync(path_cost, b.path_cost, (size_t)n_starts * sizeof(long long), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
-  b.ms = t;
+  VG_HIP(b.t.collect());
   return VG_OK;
 }
 
@@ -437,7 +394,7 @@ int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len,
 // Measurement hook: the device time of the last vg_navfn or vg_nav_paths call's kernels (HIP events on the context
 // stream around them; for vg_navfn the host's reads of the round counters in between are inside)
 extern "C" int vgx_nav_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->nav.ev[0]) return VG_E_ARG;
-  *ms = ctx->nav.ms;
+  if (!ctx || !ms || !ctx->nav.t.armed()) return VG_E_ARG;
+  *ms = ctx->nav.t.ms;
   return VG_OK;
 }

@@ -87,43 +87,12 @@ __global__ void __launch_bounds__(kOccBlock) k_occ_classify(const int* __restric
 static int occ_bufs(vg_ctx* ctx, size_t cells) {
   OccBufs& b = ctx->occ;
   static_assert(sizeof(vg_occ_params) == 176 && sizeof(vg_occ_summary) == 128, "the records' documented sizes");
-  if (!b.ready) {
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.pos), (size_t)kInfoSlab * 3 * sizeof(double)));
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dirs), (size_t)kInfoMaxDirs * 3 * sizeof(double)));
-    VG_HIP(hipMalloc(&b.sum, sizeof(vg_occ_summary)));
-    for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-    b.ready = true;
-  }
-  if (cells > b.cells) {
-    if (b.planes) (void)hipFree(b.planes);
-    if (b.grid) (void)hipFree(b.grid);
-    b.planes = nullptr;
-    b.grid = nullptr;
-    b.cells = 0;
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.planes), 2 * cells * sizeof(int)));
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.grid), cells));
-    b.cells = cells;
-  }
-  return VG_OK;
-}
-
-void occ_free(vg_ctx* ctx) {
-  OccBufs& b = ctx->occ;
-  if (b.pos) (void)hipFree(b.pos);
-  if (b.dirs) (void)hipFree(b.dirs);
-  if (b.planes) (void)hipFree(b.planes);
-  if (b.grid) (void)hipFree(b.grid);
-  if (b.sum) (void)hipFree(b.sum);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = OccBufs();
-}
-
-static int occ_elapsed(vg_ctx* ctx) {
-  OccBufs& b = ctx->occ;
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, b.ev[0], b.ev[1]));
-  b.ms += t;
+  b.nx = b.ny = 0;  // (no grid to hand to vg_clearance until this call has finished)
+  VG_HIP(b.pos.reserve((size_t)kInfoSlab * 3));
+  VG_HIP(b.dirs.reserve((size_t)kInfoMaxDirs * 3));
+  VG_HIP(b.sum.reserve(1));
+  VG_HIP(b.planes.reserve(2 * cells));
+  VG_HIP(b.grid.reserve(cells));
   return VG_OK;
 }
 
@@ -134,12 +103,11 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
   OccBufs& b = ctx->occ;
   hipStream_t s = ctx->stream;
   const OccPrm q = occ_prm(prm);
-  unsigned long long* d_sum = static_cast<unsigned long long*>(b.sum);
+  unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
   int* d_free = b.planes;
   int* d_occ = b.planes + cells;
   const int slab = kInfoSlab;  // (slab D <= 2^24 lanes per launch)
-  b.ms = 0.0;
-  b.nx = b.ny = 0;  // (no grid to hand to vg_clearance until this call has finished)
+  b.t.clear();
   VG_HIP(hipMemsetAsync(b.planes, 0, 2 * cells * sizeof(int), s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_occ_summary), s));
   if (M > 0) VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -147,24 +115,24 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
     const int m = M - i0 < slab ? M - i0 : slab;
     const int n = m * D;
     VG_HIP(hipMemcpyAsync(b.pos, positions + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VG_HIP(hipEventRecord(b.ev[0], s));
+    VG_HIP(b.t.begin(s));
     k_occ_cast<<<(n + kOccBlock - 1) / kOccBlock, kOccBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, n, q, d_free,
                                                                      d_occ, d_sum);
-    VG_HIP(hipEventRecord(b.ev[1], s));
+    VG_HIP(b.t.end(s));
     VG_HIP(hipGetLastError());
     VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
-    VG_TRY(occ_elapsed(ctx));
+    VG_HIP(b.t.collect());
   }
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   k_occ_classify<<<(int)((cells + kOccBlock - 1) / kOccBlock), kOccBlock, 0, s>>>(d_free, d_occ, (int)cells, q.min_occ,
                                                                                   q.min_free, q.occ_ratio, b.grid, d_sum);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(grid, b.grid, cells, hipMemcpyDeviceToHost, s));
   if (counts) VG_HIP(hipMemcpyAsync(counts, b.planes, 2 * cells * sizeof(int), hipMemcpyDeviceToHost, s));
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_occ_summary), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
-  VG_TRY(occ_elapsed(ctx));
+  VG_HIP(b.t.collect());
   out->n_rays = (int64_t)M * (int64_t)D;
   b.nx = prm->nx, b.ny = prm->ny;
   return VG_OK;
@@ -175,7 +143,7 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
 // Measurement hook: the device time of the last vg_occupancy call's kernels, summed over its slabs and the
 // classification (HIP events on the context stream around them)
 extern "C" int vgx_occ_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->occ.ev[0]) return VG_E_ARG;
-  *ms = ctx->occ.ms;
+  if (!ctx || !ms || !ctx->occ.t.armed()) return VG_E_ARG;
+  *ms = ctx->occ.t.ms;
   return VG_OK;
 }

@@ -199,21 +199,6 @@ int places_dirs(const vg_places_params* prm, double* out, int cap, int* count) {
   return VG_OK;
 }
 
-void places_free(PlaceIndex* I) {
-  void* p[] = {I->d_pos, I->d_dirs, I->d_desc, I->d_hit, I->d_sum, I->d_cnt, I->d_scan, I->d_scan_valid,
-               I->d_best, I->d_scores};
-  for (void* q : p)
-    if (q) (void)hipFree(q);
-  for (auto& e : I->ev)
-    if (e) (void)hipEventDestroy(e);
-  I->d_pos = I->d_dirs = nullptr;
-  I->d_desc = I->d_scan = nullptr;
-  I->d_hit = I->d_scan_valid = I->d_best = I->d_scores = nullptr;
-  I->d_sum = nullptr;
-  I->d_cnt = nullptr;
-  for (auto& e : I->ev) e = nullptr;
-}
-
 int places_build_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp) {
   static_assert(sizeof(vg_place_candidate) == 48 && sizeof(vg_places_params) == 144, "the records' documented sizes");
   PlacePrm q;
@@ -222,16 +207,15 @@ int places_build_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp) {
   I->A = q.n_az;
   I->E = q.n_el;
   hipStream_t s = ctx->stream;
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_pos), (size_t)M * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_dirs), (size_t)nb * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_desc), (size_t)M * nb * sizeof(uint16_t)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_hit), (size_t)M * sizeof(int)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_sum), (size_t)nb * sizeof(unsigned long long)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_cnt), (size_t)nb * sizeof(unsigned)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_scan), (size_t)nb * sizeof(uint16_t)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_scan_valid), sizeof(int)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_best), (size_t)M * 4 * sizeof(int)));
-  for (auto& e : I->ev) VG_HIP(hipEventCreate(&e));
+  VG_HIP(I->d_pos.reserve((size_t)M * 3));
+  VG_HIP(I->d_dirs.reserve((size_t)nb * 3));
+  VG_HIP(I->d_desc.reserve((size_t)M * nb));
+  VG_HIP(I->d_hit.reserve((size_t)M));
+  VG_HIP(I->d_sum.reserve((size_t)nb));
+  VG_HIP(I->d_cnt.reserve((size_t)nb));
+  VG_HIP(I->d_scan.reserve((size_t)nb));
+  VG_HIP(I->d_scan_valid.reserve(1));
+  VG_HIP(I->d_best.reserve((size_t)M * 4));
   // the table of vg_places_dirs as (ex, ey, up) combinations: the table itself where gravity is along -z
   std::vector<double> dirs((size_t)nb * 3);
   const double* f = I->frame;
@@ -246,10 +230,10 @@ int places_build_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp) {
   VG_HIP(hipMemcpyAsync(I->d_dirs, dirs.data(), dirs.size() * sizeof(double), hipMemcpyHostToDevice, s));
   VG_HIP(hipMemsetAsync(I->d_hit, 0, (size_t)M * sizeof(int), s));
   const int bpp = (nb + kPlaceBlock - 1) / kPlaceBlock;
-  VG_HIP(hipEventRecord(I->ev[0], s));
+  VG_HIP(I->t_build.begin(s));
   k_place_cast<<<(unsigned)M * (unsigned)bpp, kPlaceBlock, 0, s>>>(mp.vs, ctx->map, I->d_pos, I->d_dirs, nb, bpp, q.ray,
                                                                    I->d_desc, I->d_hit);
-  VG_HIP(hipEventRecord(I->ev[1], s));
+  VG_HIP(I->t_build.end(s));
   VG_HIP(hipGetLastError());
   I->hit.assign((size_t)M, 0);
   VG_HIP(hipMemcpyAsync(I->hit.data(), I->d_hit, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -266,7 +250,7 @@ int places_scan_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp, const float* xyz, 
   const int nb = q.n_az * q.n_el;
   VG_TRY(ray_bufs(ctx));
   RayBufs& b = ctx->ray;
-  if (n > b.cap) return VG_E_ARG;
+  if (n > (int)b.out.cap) return VG_E_ARG;
   hipStream_t s = ctx->stream;
   PlaceFrame F;
   memcpy(F.f, I->frame, sizeof(F.f));
@@ -275,17 +259,16 @@ int places_scan_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp, const float* xyz, 
   memcpy(eR.a, mp.extR, 72);
   const M3 Mx = mul(Rl, eR);
   memcpy(F.m, Mx.a, 72);
-  float* d_xyz = reinterpret_cast<float*>(b.dir);
+  float* d_xyz = reinterpret_cast<float*>(b.dir.p);
   if (n > 0) VG_HIP(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-  VG_HIP(hipEventRecord(I->ev[2], s));
-  I->queried = true;
+  VG_HIP(I->t_query.begin(s));
   VG_HIP(hipMemsetAsync(I->d_sum, 0, (size_t)nb * sizeof(unsigned long long), s));
   VG_HIP(hipMemsetAsync(I->d_cnt, 0, (size_t)nb * sizeof(unsigned), s));
   if (n > 0)
     k_place_scan<<<(n + kPlaceBlock - 1) / kPlaceBlock, kPlaceBlock, 2 * (size_t)nb * sizeof(unsigned), s>>>(
         d_xyz, n, q, F, I->d_sum, I->d_cnt);
   k_place_scan_finish<<<1, kPlaceBlock, 0, s>>>(I->d_sum, I->d_cnt, nb, I->d_scan, I->d_scan_valid);
-  VG_HIP(hipEventRecord(I->ev[3], s));
+  VG_HIP(I->t_query.end(s));
   VG_HIP(hipGetLastError());
   if (desc) VG_HIP(hipMemcpyAsync(desc, I->d_scan, (size_t)nb * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
   if (n_per_bin) {
@@ -304,11 +287,10 @@ int places_match_dev(vg_ctx* ctx, PlaceIndex* I, int* best, int32_t* scores_all)
   if (!place_prm(&I->prm, q)) return VG_E_ARG;
   const int nb = q.n_az * q.n_el, M = I->M;
   hipStream_t s = ctx->stream;
-  if (scores_all && !I->d_scores)
-    VG_HIP(hipMalloc(reinterpret_cast<void**>(&I->d_scores), (size_t)M * q.n_az * sizeof(int)));
+  if (scores_all) VG_HIP(I->d_scores.reserve((size_t)M * q.n_az));
   k_place_match<<<M, kPlaceBlock, 3 * (size_t)nb * sizeof(uint16_t), s>>>(
-      I->d_desc, I->d_hit, I->d_scan, q.n_az, q.n_el, q.min_bins, q.clip_q, I->d_best, scores_all ? I->d_scores : nullptr);
-  VG_HIP(hipEventRecord(I->ev[3], s));
+      I->d_desc, I->d_hit, I->d_scan, q.n_az, q.n_el, q.min_bins, q.clip_q, I->d_best, scores_all ? I->d_scores.p : nullptr);
+  VG_HIP(I->t_query.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(best, I->d_best, (size_t)M * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   if (scores_all)
@@ -328,15 +310,15 @@ extern "C" int vgx_places_ms(vg_ctx* ctx, double* build_ms, double* query_ms) {
   std::lock_guard<std::mutex> lock(owner->places_mu);
   vg::PlaceIndex* I = owner->places;
   if (!I) return VG_E_STATE;
-  float t = 0;
   if (build_ms) {
-    VG_HIP(hipEventElapsedTime(&t, I->ev[0], I->ev[1]));
-    *build_ms = t;
+    I->t_build.clear();
+    VG_HIP(I->t_build.collect());
+    *build_ms = I->t_build.ms;
   }
   if (query_ms) {
-    t = 0;
-    if (I->queried) VG_HIP(hipEventElapsedTime(&t, I->ev[2], I->ev[3]));  // (0: no query yet)
-    *query_ms = t;
+    I->t_query.clear();
+    if (I->t_query.armed()) VG_HIP(I->t_query.collect());  // (0: no query yet)
+    *query_ms = I->t_query.ms;
   }
   return VG_OK;
 }

@@ -90,14 +90,10 @@ int host_places_build(vg_ctx* ctx, const double* positions, int M, const vg_plac
   I->spacing = nn_spacing(I->pos, M, I->frame);
   const int r = places_build_dev(ctx, I, hp(ctx)->mpd);
   if (r != VG_OK) {
-    places_free(I);
     delete I;
     return r;
   }
-  if (ctx->places) {  // replaced only once the new one stands
-    places_free(ctx->places);
-    delete ctx->places;
-  }
+  delete ctx->places;  // replaced only once the new one stands
   ctx->places = I;
   return VG_OK;
 }
@@ -110,7 +106,6 @@ int host_places_end(vg_ctx* ctx) {
   if (!ctx->places) return state_err(ctx, who, "the context has no place index");
   PlaceIndex* I = ctx->places;
   ctx->places = nullptr;
-  places_free(I);
   delete I;
   return VG_OK;
 }

@@ -79,15 +79,12 @@ void diff_sum_launch(hipStream_t s, const double* absv, int n, vg_diff_summary* 
 
 int ray_bufs(vg_ctx* ctx) {
   RayBufs& b = ctx->ray;
-  if (b.cap > 0) return VG_OK;
   const size_t cap = (size_t)(ctx->cap.max_points_per_scan > 0 ? ctx->cap.max_points_per_scan : 1);
   static_assert(sizeof(vg_ray_hit) == 64 && sizeof(vg_diff_point) == 32, "the records' documented sizes");
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.org), cap * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(reinterpret_cast<void**>(&b.dir), cap * 3 * sizeof(double)));
-  VG_HIP(hipMalloc(&b.out, cap * sizeof(vg_ray_hit)));
-  VG_HIP(hipMalloc(&b.sum, sizeof(vg_diff_summary)));
-  for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-  b.cap = (int)cap;
+  VG_HIP(b.org.reserve(cap * 3));
+  VG_HIP(b.dir.reserve(cap * 3));
+  VG_HIP(b.out.reserve(cap));
+  VG_HIP(b.sum.reserve(1));
   return VG_OK;
 }
 
@@ -99,16 +96,17 @@ int raycast_dev(vg_ctx* ctx, const MP& mp, const double* origins, int n_origins,
   hipStream_t s = ctx->stream;
   const RayPrm q = ray_prm(prm);
   const int shared = n_origins == 1 && n > 1 ? 1 : 0;
-  vg_ray_hit* d_out = static_cast<vg_ray_hit*>(b.out);
+  vg_ray_hit* d_out = b.out;
+  const int cap = (int)b.out.cap;
   if (shared) VG_HIP(hipMemcpyAsync(b.org, origins, 3 * sizeof(double), hipMemcpyHostToDevice, s));
-  for (int i0 = 0; i0 < n; i0 += b.cap) {
-    const int m = n - i0 < b.cap ? n - i0 : b.cap;
+  for (int i0 = 0; i0 < n; i0 += cap) {
+    const int m = n - i0 < cap ? n - i0 : cap;
     if (!shared)
       VG_HIP(hipMemcpyAsync(b.org, origins + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     VG_HIP(hipMemcpyAsync(b.dir, dirs + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VG_HIP(hipEventRecord(b.ev[0], s));
+    VG_HIP(b.t.begin(s));
     k_raycast<<<(m + kRayBlock - 1) / kRayBlock, kRayBlock, 0, s>>>(mp.vs, ctx->map, b.org, shared, b.dir, m, q, d_out);
-    VG_HIP(hipEventRecord(b.ev[1], s));
+    VG_HIP(b.t.end(s));
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(out + i0, d_out, (size_t)m * sizeof(vg_ray_hit), hipMemcpyDeviceToHost, s));
     VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
@@ -126,16 +124,16 @@ int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
   const DiffPrm q = diff_prm(prm);
   Pose12 pose;
   for (int e = 0; e < 12; e++) pose.v[e] = pose12[e];
-  float* d_xyz = reinterpret_cast<float*>(b.dir);
-  vg_diff_point* d_pp = per_point ? static_cast<vg_diff_point*>(b.out) : nullptr;
-  vg_diff_summary* d_sum = static_cast<vg_diff_summary*>(b.sum);
+  float* d_xyz = reinterpret_cast<float*>(b.dir.p);
+  vg_diff_point* d_pp = per_point ? reinterpret_cast<vg_diff_point*>(b.out.p) : nullptr;
+  vg_diff_summary* d_sum = b.sum;
   VG_HIP(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_diff_summary), s));
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   k_scan_diff<<<(n + kRayBlock - 1) / kRayBlock, kRayBlock, 0, s>>>(mp, ctx->map, d_xyz, n, pose, q, d_pp, b.org,
                                                                    reinterpret_cast<int*>(d_sum));
   diff_sum_launch(s, b.org, n, d_sum);
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(out, d_sum, sizeof(vg_diff_summary), hipMemcpyDeviceToHost, s));
   if (per_point) VG_HIP(hipMemcpyAsync(per_point, d_pp, (size_t)n * sizeof(vg_diff_point), hipMemcpyDeviceToHost, s));
@@ -143,25 +141,15 @@ int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
   return VG_OK;
 }
 
-void ray_free(vg_ctx* ctx) {
-  RayBufs& b = ctx->ray;
-  if (b.org) (void)hipFree(b.org);
-  if (b.dir) (void)hipFree(b.dir);
-  if (b.out) (void)hipFree(b.out);
-  if (b.sum) (void)hipFree(b.sum);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = RayBufs();
-}
-
 }  // namespace vg
 
 // Test / measurement hook: the device time of the last vg_raycast slab's or
 // vg_scan_diff call's kernels (HIP events on the context stream around them)
 extern "C" int vgx_ray_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->ray.ev[0]) return VG_E_ARG;
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, ctx->ray.ev[0], ctx->ray.ev[1]));
-  *ms = t;
+  if (!ctx || !ms || !ctx->ray.t.armed()) return VG_E_ARG;
+  vg::KernelTimer& t = ctx->ray.t;
+  t.clear();
+  VG_HIP(t.collect());
+  *ms = t.ms;
   return VG_OK;
 }

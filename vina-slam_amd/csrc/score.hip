@@ -186,23 +186,6 @@ __global__ void __launch_bounds__(64) k_score_normal_sum(const double* __restric
 
 // ---- host side
 
-// scratch of at least `need` elements of `elem` bytes (doubling from 1024)
-static int score_grow_raw(vg_ctx* ctx, void** p, size_t& cap, size_t need, size_t elem) {
-  if (need <= cap && *p) return VG_OK;
-  size_t c = cap ? cap : 1024;
-  while (c < need) c *= 2;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  cap = 0;
-  VG_HIP(hipMalloc(p, c * elem));
-  cap = c;
-  return VG_OK;
-}
-template <class T>
-static int score_grow(vg_ctx* ctx, T*& p, size_t& cap, size_t need) {
-  return score_grow_raw(ctx, reinterpret_cast<void**>(&p), cap, need, sizeof(T));
-}
-
 static PoseVar pose_var_arg(const double* pose_var) {
   PoseVar pv;
   for (int e = 0; e < 18; e++) pv.v[e] = pose_var ? pose_var[e] : 0.0;
@@ -212,7 +195,7 @@ static PoseVar pose_var_arg(const double* pose_var) {
 static int score_upload(vg_ctx* ctx, const float* xyz, int n) {
   ScoreBufs& b = ctx->score;
   if (!xyz) return VG_OK;
-  VG_TRY(score_grow(ctx, b.xyz, b.cap_pts, (size_t)(n > 0 ? n : 1) * 3));
+  VG_HIP(b.xyz.reserve_pow2((size_t)(n > 0 ? n : 1) * 3));
   if (n > 0) VG_HIP(hipMemcpyAsync(b.xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   b.n = n;
   return VG_OK;
@@ -232,24 +215,22 @@ int score_poses_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const do
   slab = slab / kScoreTile * kScoreTile;
   if (slab < (size_t)kScoreTile) slab = kScoreTile;
   if (slab > (size_t)K) slab = (size_t)K;
-  if (!b.ev[0])
-    for (auto& e : b.ev) VG_HIP(hipEventCreate(&e));
-  VG_TRY(score_grow(ctx, b.poses, b.cap_poses, (size_t)K * 12));
-  VG_TRY(score_grow(ctx, b.partials, b.cap_part, (size_t)nchunks * slab * kScoreVals));
-  VG_TRY(score_grow_raw(ctx, &b.out, b.cap_out, (size_t)K, sizeof(vg_pose_score)));
-  if (per_point) VG_TRY(score_grow_raw(ctx, &b.pp, b.cap_pp, (size_t)n, sizeof(vg_point_match)));
-  vg_pose_score* d_out = static_cast<vg_pose_score*>(b.out);
-  vg_point_match* d_pp = per_point ? static_cast<vg_point_match*>(b.pp) : nullptr;
+  VG_HIP(b.poses.reserve_pow2((size_t)K * 12));
+  VG_HIP(b.partials.reserve_pow2((size_t)nchunks * slab * kScoreVals));
+  VG_HIP(b.out.reserve_pow2((size_t)K));
+  if (per_point) VG_HIP(b.pp.reserve_pow2((size_t)n));
+  vg_pose_score* d_out = b.out;
+  vg_point_match* d_pp = per_point ? b.pp.p : nullptr;
   VG_HIP(hipMemcpyAsync(b.poses, poses, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, s));
   const PoseVar pv = pose_var_arg(pose_var);
-  VG_HIP(hipEventRecord(b.ev[0], s));
+  VG_HIP(b.t.begin(s));
   for (int k0 = 0; k0 < K; k0 += (int)slab) {
     const int kn = K - k0 < (int)slab ? K - k0 : (int)slab;
     const dim3 grid(nchunks, (kn + kScoreTile - 1) / kScoreTile);
     k_score<<<grid, kScoreChunk, 0, s>>>(mp, ctx->map, b.xyz, n, b.poses, k0, kn, pv, b.partials, d_pp);
     k_score_sum<<<(kn + 255) / 256, 256, 0, s>>>(b.partials, nchunks, k0, kn, d_out);
   }
-  VG_HIP(hipEventRecord(b.ev[1], s));
+  VG_HIP(b.t.end(s));
   VG_HIP(hipGetLastError());
   VG_HIP(hipMemcpyAsync(out, d_out, (size_t)K * sizeof(vg_pose_score), hipMemcpyDeviceToHost, s));
   if (per_point) VG_HIP(hipMemcpyAsync(per_point, d_pp, (size_t)n * sizeof(vg_point_match), hipMemcpyDeviceToHost, s));
@@ -264,7 +245,7 @@ int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const doub
   for (int j = 0; j < kIekfVals; j++) out34[j] = 0.0;
   if (n <= 0) return VG_OK;
   const int nchunks = (n + kScoreChunk - 1) / kScoreChunk;
-  VG_TRY(score_grow(ctx, b.partials, b.cap_part, (size_t)nchunks * kIekfVals + kIekfVals));
+  VG_HIP(b.partials.reserve_pow2((size_t)nchunks * kIekfVals + kIekfVals));
   PoseVar pose;
   for (int e = 0; e < 12; e++) pose.v[e] = pose12[e];
   for (int e = 12; e < 18; e++) pose.v[e] = 0.0;
@@ -277,26 +258,15 @@ int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const doub
   return VG_OK;
 }
 
-void score_free(vg_ctx* ctx) {
-  ScoreBufs& b = ctx->score;
-  if (b.xyz) (void)hipFree(b.xyz);
-  if (b.poses) (void)hipFree(b.poses);
-  if (b.partials) (void)hipFree(b.partials);
-  if (b.out) (void)hipFree(b.out);
-  if (b.pp) (void)hipFree(b.pp);
-  for (auto& e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = ScoreBufs();
-}
-
 }  // namespace vg
 
 // Test / measurement hook: the device time of the last vg_score_poses call's
 // kernels (HIP events on the context stream around them)
 extern "C" int vgx_score_ms(vg_ctx* ctx, double* ms) {
-  if (!ctx || !ms || !ctx->score.ev[0]) return VG_E_ARG;
-  float t = 0;
-  VG_HIP(hipEventElapsedTime(&t, ctx->score.ev[0], ctx->score.ev[1]));
-  *ms = t;
+  if (!ctx || !ms || !ctx->score.t.armed()) return VG_E_ARG;
+  vg::KernelTimer& t = ctx->score.t;
+  t.clear();
+  VG_HIP(t.collect());
+  *ms = t.ms;
   return VG_OK;
 }

@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/vina_gpu.h"
 #include "vg_la.h"
+#include "vg_scratch.h"
 
 #define VG_HIP(call)                                                                    \
   do {                                                                                  \
@@ -385,98 +386,86 @@ struct BaLoop {
   int seq0 = 0, enq = 0, tail_at = 0, k = 0;  // first iteration flag number, iterations enqueued, ahead of the tail, next k
   bool active = false;
 };
+// The query-side scratch below is made of DevBuf / KernelTimer members
+// (vg_scratch.h): each buffer is reserved where it is first needed and freed by
+// its owner's destructor (delete ctx, or the change layer's / place index's delete)
+//
 // vg_score_poses / vg_relocalize scratch (score.hip): allocated on first use,
-// grown geometrically, freed by vg_destroy (score_free)
+// grown geometrically (reserve_pow2)
 struct ScoreBufs {
-  float* xyz = nullptr;       // the scored cloud, n x 3 as the caller gave it
-  double* poses = nullptr;    // K x 12
-  double* partials = nullptr; // [chunk][pose of the slab][kScoreVals], or [chunk][34] (the normal equations)
-  void* out = nullptr;        // K vg_pose_score records; the 34 reduced sums
-  void* pp = nullptr;         // n vg_point_match records
-  size_t cap_pts = 0, cap_poses = 0, cap_part = 0, cap_out = 0, cap_pp = 0;
-  int n = 0;                  // points of the cloud in xyz
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last vg_score_poses call's kernels (vgx_score_ms)
+  DevBuf<float> xyz;           // the scored cloud, n x 3 as the caller gave it
+  DevBuf<double> poses;        // K x 12
+  DevBuf<double> partials;     // [chunk][pose of the slab][kScoreVals], or [chunk][34] + the 34 reduced sums (the normal equations)
+  DevBuf<vg_pose_score> out;   // K records
+  DevBuf<vg_point_match> pp;   // n records
+  int n = 0;                   // points of the cloud in xyz
+  KernelTimer t;               // around the last vg_score_poses call's kernels (vgx_score_ms)
 };
-// vg_raycast / vg_scan_diff staging (raycast.hip): one slab of cap =
-// max_points_per_scan rays, allocated on first use, freed by vg_destroy (ray_free)
+// vg_raycast / vg_scan_diff staging (raycast.hip): one slab of
+// max_points_per_scan rays (out.cap), allocated on first use
 struct RayBufs {
-  double* org = nullptr;   // cap x 3 origins (vg_scan_diff: the points' |m.range - r| terms)
-  double* dir = nullptr;   // cap x 3 directions (vg_scan_diff: the cloud, n x 3 floats)
-  void* out = nullptr;     // cap vg_ray_hit records (vg_scan_diff: vg_diff_point records)
-  void* sum = nullptr;     // one vg_diff_summary
-  int cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last call's kernels (vgx_ray_ms)
+  DevBuf<double> org;      // cap x 3 origins (vg_scan_diff: the points' |m.range - r| terms)
+  DevBuf<double> dir;      // cap x 3 directions (vg_scan_diff: the cloud, n x 3 floats)
+  DevBuf<vg_ray_hit> out;  // cap records (vg_scan_diff: vg_diff_point records, half the size)
+  DevBuf<vg_diff_summary> sum;  // one
+  KernelTimer t;           // around the last call's kernels (vgx_ray_ms)
 };
-// vg_localizability / vg_scan_info staging (localizability.hip), allocated on first
-// use, freed by vg_destroy (info_free)
+// vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
 constexpr int kInfoSlab = 4096;     // places per launch of k_info_places
 constexpr int kInfoMaxDirs = 4096;  // D's limit
+struct InfoPart;                    // localizability.hip
 struct InfoBufs {
-  double* pos = nullptr;   // slab x 3 origins
-  double* dirs = nullptr;  // kInfoMaxDirs x 3 directions
-  void* out = nullptr;     // slab vg_info_rec records (vg_scan_info: the first)
-  void* part = nullptr;    // vg_scan_info: one InfoPart per workgroup of max_points_per_scan points
-  int slab = 0;            // 0: not allocated
-  int slab_want = 0;       // vgx_info_slab (0: kInfoSlab)
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
-  double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_info_ms)
+  DevBuf<double> pos;        // slab x 3 origins
+  DevBuf<double> dirs;       // kInfoMaxDirs x 3 directions
+  DevBuf<vg_info_rec> out;   // slab records (vg_scan_info: the first)
+  DevBuf<InfoPart> part;     // vg_scan_info: one per workgroup of max_points_per_scan points
+  int slab_want = 0;         // vgx_info_slab (0: kInfoSlab)
+  KernelTimer t;             // around a launch's kernels; ms: the last call's, summed over its slabs (vgx_info_ms)
 };
 // vg_occupancy staging (occupancy.hip), allocated on first use and grown to the
-// largest grid asked for, freed by vg_destroy (occ_free)
+// largest grid asked for
 struct OccBufs {
-  double* pos = nullptr;   // kInfoSlab x 3 origins
-  double* dirs = nullptr;  // kInfoMaxDirs x 3 directions
-  int* planes = nullptr;   // 2 x cells: n_free, then n_occ
-  int8_t* grid = nullptr;  // cells
-  void* sum = nullptr;     // one vg_occ_summary
-  size_t cells = 0;        // capacity of planes / grid, in cells
+  DevBuf<double> pos;      // kInfoSlab x 3 origins
+  DevBuf<double> dirs;     // kInfoMaxDirs x 3 directions
+  DevBuf<int> planes;      // 2 x cells: n_free, then n_occ
+  DevBuf<int8_t> grid;     // cells
+  DevBuf<vg_occ_summary> sum;  // one
   int nx = 0, ny = 0;      // the grid the last call left in `grid` (0: none yet); vg_clearance's grid == NULL reads it
-  bool ready = false;      // pos, dirs, sum and the events exist
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around a launch's kernels
-  double ms = 0.0;         // the last call's kernels, summed over its slabs (vgx_occ_ms)
+  KernelTimer t;           // around a launch's kernels; ms: the last call's, summed over its slabs (vgx_occ_ms)
 };
 // vg_clearance staging (clearance.hip), allocated on first use and grown to the
-// largest grid asked for, freed by vg_destroy (clr_free). dist2 / nearest / cost
-// exist only once a call asked for that output
+// largest grid asked for (grid.cap cells: when it grows, the other planes go). dist2 /
+// nearest / cost exist only once a call asked for that output
 struct ClrBufs {
-  int8_t* grid = nullptr;    // cells: a host grid's upload (grid == NULL reads OccBufs::grid instead)
-  int16_t* dy = nullptr;     // cells: k_clr_cols' plane, oy - iy of the column's nearest obstacle (kClrNone: none)
-  int* dist2 = nullptr;      // cells
-  int* nearest = nullptr;    // cells
-  uint8_t* cost = nullptr;   // cells
+  DevBuf<int8_t> grid;       // cells: a host grid's upload (grid == NULL reads OccBufs::grid instead)
+  DevBuf<int16_t> dy;        // cells: k_clr_cols' plane, oy - iy of the column's nearest obstacle (kClrNone: none)
+  DevBuf<int> dist2;         // cells
+  DevBuf<int> nearest;       // cells
+  DevBuf<uint8_t> cost;      // cells
   int nx = 0, ny = 0;        // the plane the last call that asked for `cost` left there (0: none); vg_navfn's cost == NULL reads it
-  uint8_t* table = nullptr;  // the cost by dist2, table_n entries
-  void* sum = nullptr;       // one vg_clr_summary
-  size_t cells = 0;          // capacity of grid / dy, and of the three outputs where they exist
-  size_t table_cap = 0;      // capacity of table, in entries
+  DevBuf<uint8_t> table;     // the cost by dist2, table_n entries
+  DevBuf<vg_clr_summary> sum;  // one
   int table_n = 0;           // entries in use; 0: none built yet
   double table_key[4] = {0, 0, 0, 0};  // res, inscribed_radius, inflation_radius, cost_scaling the table was built from
-  bool ready = false;        // sum and the events exist
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the call's kernels
-  double ms = 0.0;           // the last call's kernels (vgx_clr_ms)
+  KernelTimer t;             // around the call's kernels; ms: the last call's (vgx_clr_ms)
 };
 // vg_navfn / vg_nav_paths planes and staging (navfn.hip), allocated on first use
-// and grown to the largest plane asked for, freed by vg_destroy (nav_free)
+// and grown to the largest plane asked for
 struct NavBufs {
-  uint8_t* cost = nullptr;    // cells: a host plane's upload (cost == NULL reads ClrBufs::cost instead)
-  uint16_t* trav = nullptr;   // cells: the price of standing on the cell, 0 impassable (k_nav_init)
-  uint32_t* pot = nullptr;    // cells: the field
-  size_t cells = 0;           // capacity of cost / trav / pot, in cells
-  int* act = nullptr;         // two activity planes of act_cap tiles each: this round's and the next's
-  size_t act_cap = 0;
-  uint16_t* table = nullptr;  // 256 entries: trav by cost byte
-  int* goals = nullptr;       // 2 kNavMaxPoints: goals (vg_navfn) or starts (vg_nav_paths)
-  unsigned* marks = nullptr;  // kNavBatchMax counters, one per round of a batch: tiles that woke a neighbour
-  void* sum = nullptr;        // one vg_nav_summary
-  int* cells_out = nullptr;   // vg_nav_paths: n_starts max_len path cells
-  size_t cells_out_cap = 0;
-  int* len = nullptr;         // kNavMaxPoints each: len, status; path_cost
-  int* status = nullptr;
-  long long* path_cost = nullptr;
+  DevBuf<uint8_t> cost;       // cells: a host plane's upload (cost == NULL reads ClrBufs::cost instead)
+  DevBuf<uint16_t> trav;      // cells: the price of standing on the cell, 0 impassable (k_nav_init)
+  DevBuf<uint32_t> pot;       // cells: the field
+  DevBuf<int> act;            // two activity planes of act.cap / 2 tiles each: this round's and the next's
+  DevBuf<uint16_t> table;     // 256 entries: trav by cost byte
+  DevBuf<int> goals;          // 2 kNavMaxPoints: goals (vg_navfn) or starts (vg_nav_paths)
+  DevBuf<unsigned> marks;     // kNavBatchMax counters, one per round of a batch: tiles that woke a neighbour
+  DevBuf<vg_nav_summary> sum; // one
+  DevBuf<int> cells_out;      // vg_nav_paths: n_starts max_len path cells
+  DevBuf<int> len;            // kNavMaxPoints each: len, status; path_cost
+  DevBuf<int> status;
+  DevBuf<long long> path_cost;
   int nx = 0, ny = 0;         // the field the last vg_navfn call left in `pot` (0: none)
-  bool ready = false;         // table, goals, marks, sum, len, status, path_cost and the events exist
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the call's kernels
-  double ms = 0.0;            // the last call's kernels (vgx_nav_ms)
+  KernelTimer t;              // around the call's kernels; ms: the last call's (vgx_nav_ms)
 };
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
@@ -489,7 +478,7 @@ struct ChangeCell {  // 40 B per slot of the cell table (the slot's key: ChangeD
   int n_appeared, n_scans, last_epoch, pad;
 };
 enum { kChgDropped = 0, kChgOutOfRange = 1, kChgTot = 2 };
-struct ChangeDev {   // what the kernels take
+struct ChangeDev {   // what the kernels take: views of the layer's buffers
   ChangeNode* node = nullptr;          // cap_nodes
   unsigned long long* ckey = nullptr;  // mask + 1 packed cell keys, kKeyEmpty: free
   ChangeCell* cell = nullptr;          // mask + 1
@@ -502,10 +491,12 @@ struct ChangeLayer {
   vg_diff_params diff;   // as vg_change_begin was given them
   int epoch = 0;         // accumulate calls that succeeded so far
   long long calls = 0, points = 0, cls[4] = {0, 0, 0, 0};
-  int* d_blk = nullptr;  // the report's per-workgroup counts / offsets (blk_n entries)
-  int blk_n = 0;
-  void* d_out = nullptr; // the report's record staging, grown on demand
-  size_t out_bytes = 0;
+  DevBuf<ChangeNode> node;  // the layer's device memory (d's pointers), freed with the layer
+  DevBuf<unsigned long long> ckey;
+  DevBuf<ChangeCell> cell;
+  DevBuf<long long> tot;
+  DevBuf<int> blk;       // the report's per-workgroup counts / offsets
+  DevBuf<char> out;      // the report's record staging (bytes), grown on demand
 };
 // The place index (vina_gpu.h "Place index"; places.hip, places_host.cpp): a side
 // structure of the context that owns a frozen map, like the change layer. One
@@ -518,18 +509,18 @@ struct PlaceIndex {
   double spacing = 0.0;       // median nearest-neighbour distance of the places in the ex-ey plane (0: M == 1)
   std::vector<double> pos;    // M x 3, as given
   std::vector<int> hit;       // per place: its hit bins
-  double* d_pos = nullptr;    // M x 3
-  double* d_dirs = nullptr;   // A E x 3, world
-  uint16_t* d_desc = nullptr; // M x E x A
-  int* d_hit = nullptr;       // M
-  unsigned long long* d_sum = nullptr;  // A E: the scan's sums of q
-  unsigned* d_cnt = nullptr;  // A E: its points per bin
-  uint16_t* d_scan = nullptr; // A E: its descriptor
-  int* d_scan_valid = nullptr;  // its non-empty bins
-  int* d_best = nullptr;      // M x 4: best shift, its score, second shift, its score
-  int* d_scores = nullptr;    // M x A, allocated on the first request
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the build's kernel; around the last query's
-  bool queried = false;       // ev[2], ev[3] have been recorded
+  DevBuf<double> d_pos;       // M x 3
+  DevBuf<double> d_dirs;      // A E x 3, world
+  DevBuf<uint16_t> d_desc;    // M x E x A
+  DevBuf<int> d_hit;          // M
+  DevBuf<unsigned long long> d_sum;  // A E: the scan's sums of q
+  DevBuf<unsigned> d_cnt;     // A E: its points per bin
+  DevBuf<uint16_t> d_scan;    // A E: its descriptor
+  DevBuf<int> d_scan_valid;   // its non-empty bins
+  DevBuf<int> d_best;         // M x 4: best shift, its score, second shift, its score
+  DevBuf<int> d_scores;       // M x A, allocated on the first request
+  KernelTimer t_build;        // around the build's kernel
+  KernelTimer t_query;        // around the last query's kernels, scan pass to match pass (armed: a query has run)
 };
 // window view for the map kernels, built on the device from DState::xs
 struct WinArg {
@@ -602,8 +593,8 @@ struct vg_ctx {
   bool overlap_iekf = true;  // the next IEKF under the margi remainder (lio_state_estimation)
   int pub_flags = 0;         // vg_set_publish: bit 0 = /map_cmap after each window BA (k_local_map),
                              // bit 1 = the /voxel_plane + /voxel_normal events after each recut (markers.hip)
-  vg_plane_marker* d_mk = nullptr;  // the last collection's event records (allocated while bit 1 is set)
-  int* d_mk_cnt = nullptr;          // [0] events reserved by the last collection (past mk_cap: deferred)
+  vg::DevBuf<vg_plane_marker> d_mk;  // the last collection's event records (allocated while bit 1 is set)
+  vg::DevBuf<int> d_mk_cnt;          // [0] events reserved by the last collection (past mk_cap: deferred)
   int mk_cap = 1 << 16;             // vg_marker_capacity
   bool mk_fresh = false;            // the last opened scan ran a collection
   bool mk_keep = false;             // a checkpoint load brought the nodes' publication flags: the next enable keeps them
@@ -1043,7 +1034,6 @@ int markers_enable(vg_ctx* ctx, bool on);  // blank slate either way; the event 
 int markers_collect(vg_ctx* ctx);          // one collection over surf_map_slide, on the context stream
 int markers_read(vg_ctx* ctx, vg_plane_marker* out, int cap, int* n, int* deferred);
 int map_planes(vg_ctx* ctx, int flags, vg_plane_marker* out, int cap, int* n);
-void markers_free(vg_ctx* ctx);
 // score.hip: OctoTree::match for one cloud under K poses (host arrays in, host
 // records out; synchronous on the context stream, which the caller drained).
 // xyz == nullptr: the cloud the last call uploaded
@@ -1051,7 +1041,6 @@ int score_poses_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const do
                     const double* pose_var, vg_pose_score* out, void* per_point);
 // the IEKF's 34 sums (HTH, HTz, nnt, matches) of the uploaded cloud at one pose
 int score_normal_dev(vg_ctx* ctx, const MP& mp, const double* pose12, const double* pose_var, double* out34);
-void score_free(vg_ctx* ctx);
 // raycast.hip: rays through the map to the first plane (host arrays in, host
 // records out; synchronous on the context stream, which the caller drained)
 int raycast_dev(vg_ctx* ctx, const MP& mp, const double* origins, int n_origins, const double* dirs, int n,
@@ -1059,7 +1048,6 @@ int raycast_dev(vg_ctx* ctx, const MP& mp, const double* origins, int n_origins,
 // a scan's points against the map's expected range along their beams, at pose12
 int scan_diff_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
                   const vg_diff_params* prm, vg_diff_point* per_point, vg_diff_summary* out);
-void ray_free(vg_ctx* ctx);
 int ray_bufs(vg_ctx* ctx);  // the staging, allocated on first use
 void diff_sum_launch(hipStream_t s, const double* absv, int n, vg_diff_summary* d_sum);  // k_diff_sum
 // localizability.hip: the information matrix per place / of a scan at pose12 (host arrays in, host records out;
@@ -1068,12 +1056,10 @@ int localizability_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M
                        const vg_info_params* prm, vg_info_rec* out);
 int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const double* pose12,
                   const vg_diff_params* diff, const vg_info_params* prm, vg_info_rec* out);
-void info_free(vg_ctx* ctx);
 // occupancy.hip: the occupancy grid of M origins x D directions (host arrays in; grid, counts (or null) and
 // summary out; synchronous on the context stream, which the caller drained). prm: checked by the caller
 int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
                   const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
-void occ_free(vg_ctx* ctx);
 // clearance.hip: the clearance field and costmap of an nx x ny grid (host grid in, or null: the grid the last
 // vg_occupancy left on the device; dist2, nearest, cost (each or null) and summary out; synchronous on the
 // context stream, which the caller drained). prm: checked by the caller; table: the cost by dist2, table_n
@@ -1081,7 +1067,6 @@ void occ_free(vg_ctx* ctx);
 bool clr_table_current(const vg_ctx* ctx, const vg_clr_params* prm, int table_n);
 int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, const uint8_t* table, int table_n,
                   int32_t* dist2, int32_t* nearest, uint8_t* cost, vg_clr_summary* out);
-void clr_free(vg_ctx* ctx);
 // navfn.hip: the navigation function of an nx x ny cost plane (host plane in, or null: the plane the last
 // vg_clearance left on the device; pot (or null) and summary out) and the paths down the field it left; synchronous
 // on the context stream, which the caller drained. Arguments: checked by the caller; table: trav by cost byte
@@ -1089,10 +1074,8 @@ int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const 
               int n_goals, uint32_t* pot, vg_nav_summary* out);
 int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
                   int32_t* status, int64_t* path_cost);
-void nav_free(vg_ctx* ctx);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
-void change_free(ChangeLayer* L);
 int change_clear_dev(vg_ctx* ctx, ChangeLayer* L);
 // one scan into L at `epoch`, through ctx's map, staging and stream; x, y, z: host AoS (stride 3, dev false) or
 // device arrays (stride 1)
@@ -1106,7 +1089,6 @@ int change_report_dev(vg_ctx* ctx, ChangeLayer* L, const vg_change_query& q, std
 int places_prm_ok(const vg_places_params* prm, int* A, int* E);  // VG_E_ARG: a limit exceeded, a bad span
 int places_dirs(const vg_places_params* prm, double* out, int cap, int* count);
 int places_build_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp);  // I->prm, pos, frame, M set: allocates, casts, reads hit
-void places_free(PlaceIndex* I);
 // the scan's descriptor into I->d_scan through ctx's staging and stream; desc / n_per_bin: host copies or null
 int places_scan_dev(vg_ctx* ctx, PlaceIndex* I, const MP& mp, const float* xyz, int n, const double* R_level9,
                     uint16_t* desc, int32_t* n_per_bin, int* n_valid);

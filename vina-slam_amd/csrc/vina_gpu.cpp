@@ -329,14 +329,7 @@ int vg_destroy(vg_ctx* ctx) {
   if (ctx->arena.base) (void)hipFree(ctx->arena.base);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->dbg_cap_buf) (void)hipFree(ctx->dbg_cap_buf);
-  markers_free(ctx);
-  score_free(ctx);
-  ray_free(ctx);
-  info_free(ctx);
-  occ_free(ctx);
-  clr_free(ctx);
-  nav_free(ctx);
-  shard_free(ctx);
+  shard_free(ctx);  // (the query scratch, the markers' buffers and their timers go with `delete ctx` below)
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);
   if (ctx->host) host_free(ctx);
