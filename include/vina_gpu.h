@@ -795,6 +795,84 @@ int vg_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const u
 int vg_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells,
                  int32_t* len, int32_t* status, int64_t* path_cost);
 
+/* ---- Exploration frontiers: the free / unknown boundary, labelled and ranked -----
+ * What a robot that is still mapping heads for: the free cells of an nx x ny grid
+ * of VG_OCC_* values (i = iy nx + ix as in vg_occupancy) that touch unknown space,
+ * grouped into connected components on the device, one record per component.
+ * Everything is integer arithmetic, so every output byte is a pure function of the
+ * inputs.
+ *
+ * Cell i is a frontier cell when all of these hold:
+ *   grid[i] == VG_OCC_FREE (exactly 0; any other byte value is not free here);
+ *   at least one of its 4-neighbours inside the grid equals VG_OCC_UNKNOWN (what
+ *     lies outside the grid is not unknown);
+ *   with flags bit 0: cost[i] < cost_max, cost the VG_COST_* plane of vg_clearance;
+ *   with flags bit 1: pot[i] != VG_NAV_UNREACHED, pot the field that the last
+ *     vg_navfn call left on this context. w(a, b) is symmetric, so a field computed
+ *     with the robot's own cell as the only goal is the cost from the robot to
+ *     every cell: this test keeps what the robot can reach, and best_cell below is
+ *     the cheapest cell of a frontier to drive to.
+ * The cost test comes before the reach test: a free cell beside an unknown one
+ * that fails the cost test is counted in n_rejected_cost and not looked at again;
+ * one that passes it and fails the reach test is counted in n_rejected_unreached.
+ *
+ * A frontier is an 8-connected component of frontier cells. label[i] is the
+ * smallest linear index among the cells of i's component, -1 where i is no
+ * frontier cell. The components are found by a union-find that takes a fixed
+ * number of launches whatever their shape. */
+#define VG_FRONTIER_MAX_RECORDS 65536
+typedef struct vg_frontier_params {   /* 56 bytes, no implicit padding */
+  int    nx, ny;        /* as vg_clr_params; nx ny <= VG_OCC_MAX_CELLS, each <= VG_CLR_MAX_SIDE */
+  int    flags;         /* bit 0: the cost test; bit 1: the reach test, and best_cell */
+  int    cost_max;      /* 0: 253 (VG_COST_INSCRIBED); else 1 .. 255 (flags bit 0) */
+  int    min_size;      /* a component of fewer cells gets no record; <= 0: 1 */
+  int    pad;
+  double reserved[4];
+} vg_frontier_params;
+typedef struct vg_frontier_rec {      /* 64 bytes, no implicit padding */
+  int32_t  label, size;               /* the component's smallest linear index; its cells */
+  int32_t  x_min, y_min, x_max, y_max;
+  int64_t  sum_x, sum_y;              /* sums of ix and of iy over the component: the centroid is sum / size */
+  int32_t  best_cell;                 /* flags bit 1: the component's cell with the smallest pot, among equals the
+                                         smallest linear index; else -1 */
+  uint32_t best_pot;                  /* its pot; 0 without bit 1 */
+  int64_t  reserved[2];
+} vg_frontier_rec;
+typedef struct vg_frontier_summary {  /* 128 bytes, no implicit padding; every field is reproducible */
+  int64_t n_frontier_cells, n_components; /* frontier cells; their components */
+  int64_t n_kept, n_written;              /* components with size >= min_size; records written: min(n_kept, max_records) */
+  int64_t max_size;                       /* the largest component's cells; 0 without any */
+  int64_t cells_free, cells_unknown;      /* cells with value VG_OCC_FREE; VG_OCC_UNKNOWN */
+  int64_t n_rejected_cost, n_rejected_unreached;
+  int64_t reserved[7];
+} vg_frontier_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vg_frontier_params) == 56 && sizeof(vg_frontier_rec) == 64 && sizeof(vg_frontier_summary) == 128,
+              "the frontier records have no implicit padding");
+#else
+_Static_assert(sizeof(vg_frontier_params) == 56 && sizeof(vg_frontier_rec) == 64 && sizeof(vg_frontier_summary) == 128,
+               "the frontier records have no implicit padding");
+#endif
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call on
+ * this context left on the device (VG_E_STATE when there was no such call or its nx,
+ * ny differ from prm's). cost: consulted only with flags bit 0; nx ny uint8 on the
+ * host, or NULL: the plane that the last vg_clearance call on this context left on
+ * the device (VG_E_STATE when no call produced one or its nx, ny differ). With
+ * flags bit 1 the field of the last vg_navfn call on this context is read where it
+ * lies (VG_E_STATE without one, or when its nx, ny differ). labels: nx ny int32, or
+ * NULL: not copied out. recs: the components with size >= min_size in ascending
+ * label, the first max_records of them. All planes are device buffers allocated on
+ * first use and re-used; only labels (when asked for), the records written and
+ * the summary leave the device. NULL ctx, prm or out; nx or ny < 1 or >
+ * VG_CLR_MAX_SIDE, or nx ny > VG_OCC_MAX_CELLS; flags with a bit above 1; cost !=
+ * NULL with flags bit 0 clear; cost_max < 0 or > 255; max_records < 0 or >
+ * VG_FRONTIER_MAX_RECORDS; recs == NULL with max_records > 0: VG_E_ARG, and nothing
+ * is written. Every device loop that follows parent links is bounded by nx ny
+ * steps; were that bound ever hit the call returns VG_E_CAPACITY with nothing
+ * written. Legal where vg_clearance is. */
+int vg_frontiers(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm,
+                 int32_t* labels, vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

@@ -5,6 +5,7 @@
 // see INTEGRATION.md for the line-by-line mapping. Errors become exceptions
 // (the reference calls exit(), octree.cpp:407, optimizers.cpp:70).
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -225,6 +226,43 @@ class LioCore {
     r.len.resize(n ? n : 1), r.status.resize(n ? n : 1), r.cost.resize(n ? n : 1);
     check(vg_nav_paths(ctx_, starts.data(), (int)n, max_len, r.cells.data(), r.len.data(), r.status.data(), r.cost.data()),
           "vg_nav_paths");
+    return r;
+  }
+  // the exploration frontiers (vina_gpu.h "Exploration frontiers") of grid (nx ny cells of VG_OCC_*; null: the grid
+  // the last occupancy() call left on the device); cost (flags bit 0) null: the plane the last clearance() call left
+  // there; flags bit 1 reads the field of the last navfn() call. recs: the kept components in ascending label, at
+  // most max_records
+  struct Frontiers {
+    std::vector<int32_t> labels;  // filled only where asked for
+    std::vector<vg_frontier_rec> recs;
+    vg_frontier_summary summary;
+    // the indices of recs in the order to visit them: with best_cell >= 0 by ascending (best_pot, label), the
+    // cheapest to drive to first; otherwise by descending size, then ascending label
+    std::vector<int> order() const {
+      std::vector<int> o(recs.size());
+      for (size_t k = 0; k < o.size(); k++) o[k] = (int)k;
+      bool best = !recs.empty();
+      for (const vg_frontier_rec& r : recs) best = best && r.best_cell >= 0;
+      std::sort(o.begin(), o.end(), [&](int a, int b) {
+        const vg_frontier_rec &p = recs[a], &q = recs[b];
+        if (best && p.best_pot != q.best_pot) return p.best_pot < q.best_pot;
+        if (!best && p.size != q.size) return p.size > q.size;
+        return p.label < q.label;
+      });
+      return o;
+    }
+  };
+  Frontiers frontiers(const int8_t* grid, const uint8_t* cost, const vg_frontier_params& prm, int max_records = 4096,
+                      bool want_labels = true) {
+    Frontiers r;
+    size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    if (cells > (size_t)VG_OCC_MAX_CELLS) cells = 1;
+    if (want_labels) r.labels.resize(cells);
+    r.recs.resize(max_records > 0 && max_records <= VG_FRONTIER_MAX_RECORDS ? (size_t)max_records : 0);
+    check(vg_frontiers(ctx_, grid, cost, &prm, want_labels ? r.labels.data() : nullptr,
+                       r.recs.empty() ? nullptr : r.recs.data(), max_records, &r.summary),
+          "vg_frontiers");
+    r.recs.resize((size_t)r.summary.n_written);
     return r;
   }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the

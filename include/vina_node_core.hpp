@@ -161,6 +161,15 @@ struct Plan {
   vg_nav_summary summary = {};
 };
 
+// Where to go next while the map is still growing (NodeCore::explore_goal)
+struct ExploreGoal {
+  bool found = false;            // a frontier the robot can reach exists
+  vg_frontier_rec frontier = {}; // the chosen one: the first in LioCore::Frontiers::order()
+  double goal_xy[2] = {0, 0};    // its best_cell's centre, metres
+  Plan path;                     // from the goal's cell down to the robot's: reverse it to drive (the field is symmetric)
+  LioCore::Frontiers frontiers;  // every kept frontier and the summary (labels only where asked for)
+};
+
 class NodeCore {
  public:
   // cfg.cold_start = 1 for a run from a bag (the node's initialization,
@@ -498,6 +507,57 @@ class NodeCore {
       if (want_pot) p.pot.push_back(f.pot[(size_t)c]);
     }
     return p;
+  }
+
+  // The frontiers of the last occupancy_grid() over the last costmap() of this node, both read where they lie on
+  // the device (no vg_occupancy or vg_clearance may have run on the context since): free cells beside unknown ones
+  // whose cost is below cost_max (0: 253). use_pot: only cells that the field of the last plan() or navfn reaches,
+  // and the records carry the cheapest cell of each. Completes outstanding work.
+  LioCore::Frontiers frontiers(bool use_pot, int min_size = 0, int max_records = 4096, bool want_labels = false,
+                               int cost_max = 0) {
+    finish();
+    if (!cm_nx_) throw Error(VG_E_STATE, "frontiers: no costmap() on this node yet");
+    vg_frontier_params q = {};
+    q.nx = cm_nx_, q.ny = cm_ny_, q.flags = 1 | (use_pot ? 2 : 0), q.cost_max = cost_max, q.min_size = min_size;
+    return lio_.frontiers(nullptr, nullptr, q, max_records, want_labels);
+  }
+  // the centre of cell c of the last costmap(), metres
+  void cell_xy(int32_t c, double xy[2]) const {
+    xy[0] = cm_x0_ + (c % cm_nx_ + 0.5) * cm_res_, xy[1] = cm_y0_ + (c / cm_nx_ + 0.5) * cm_res_;
+  }
+
+  // The next goal of an exploring robot standing at robot_xy, without a plane leaving the device in between:
+  // occupancy_grid(P) -> costmap() of it where it lies -> vg_navfn with the robot's own cell as the goal (w is
+  // symmetric: the field is the cost from the robot to every cell) -> vg_frontiers with the cost and the reach
+  // test -> the first frontier in order(), the cheapest to drive to, and its best_cell as a world point ->
+  // vg_nav_paths from that cell, which descends to the robot: reverse ExploreGoal::path to drive. found is false
+  // where no frontier of at least min_size cells can be reached.
+  ExploreGoal explore_goal(const double robot_xy[2], const OccupancyGridParams& P, double inscribed, double inflation,
+                           double scaling, int min_size = 0, const vg_nav_params* prm = nullptr, int max_len = 65536) {
+    const OccupancyGrid g = occupancy_grid(P);
+    costmap(g, inscribed, inflation, scaling, 0, true);
+    vg_nav_params q = {};
+    if (prm) q = *prm;
+    q.nx = cm_nx_, q.ny = cm_ny_;
+    const double fx = std::floor((robot_xy[0] - cm_x0_) / cm_res_), fy = std::floor((robot_xy[1] - cm_y0_) / cm_res_);
+    const std::vector<int32_t> robot = {fx >= 0.0 && fx < (double)cm_nx_ ? (int32_t)fx : (int32_t)-1,
+                                        fy >= 0.0 && fy < (double)cm_ny_ ? (int32_t)fy : (int32_t)-1};
+    ExploreGoal e;
+    e.path.summary = lio_.navfn(nullptr, q, robot, false).summary;
+    e.frontiers = frontiers(true, min_size);
+    if (e.frontiers.recs.empty()) return e;
+    e.found = true;
+    e.frontier = e.frontiers.recs[(size_t)e.frontiers.order()[0]];
+    cell_xy(e.frontier.best_cell, e.goal_xy);
+    const LioCore::NavPaths r = lio_.nav_paths({e.frontier.best_cell % cm_nx_, e.frontier.best_cell / cm_nx_}, max_len);
+    e.path.status = r.status[0], e.path.cost = r.cost[0];
+    e.path.cells.assign(r.cells.begin(), r.cells.begin() + r.len[0]);
+    for (const int32_t c : e.path.cells) {
+      double xy[2];
+      cell_xy(c, xy);
+      e.path.xy.push_back(xy[0]), e.path.xy.push_back(xy[1]);
+    }
+    return e;
   }
 
   bool write_tum(const std::string& file) {

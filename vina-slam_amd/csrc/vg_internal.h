@@ -467,6 +467,20 @@ struct NavBufs {
   int nx = 0, ny = 0;         // the field the last vg_navfn call left in `pot` (0: none)
   KernelTimer t;              // around the call's kernels; ms: the last call's (vgx_nav_ms)
 };
+// vg_frontiers planes and staging (frontier.hip), allocated on first use and grown
+// to the largest grid asked for
+struct FrontierBufs {
+  DevBuf<int8_t> grid;        // cells: a host grid's upload (grid == NULL reads OccBufs::grid instead)
+  DevBuf<uint8_t> cost;       // cells: a host plane's upload (cost == NULL reads ClrBufs::cost instead)
+  DevBuf<int> parent;         // cells: the union-find forest, -1 off the frontier; after the flatten a root's dense id
+  DevBuf<int> label;          // cells: the output plane
+  DevBuf<int> counts;         // kFrMaxCounts + 1: per-workgroup counts, scanned in place (roots, then kept records)
+  DevBuf<vg_frontier_rec> rec;  // one per component, in ascending label; grown to the count a call finds
+  DevBuf<vg_frontier_rec> out;  // VG_FRONTIER_MAX_RECORDS: the records that leave
+  DevBuf<unsigned long long> sum;  // vg_frontier_summary's 16 slots, then the capacity flag
+  int combine = 1;            // k_fr_stats: lanes of a wave on one component add once (vgx_frontier_combine)
+  KernelTimer t;              // around the call's kernels; ms: the last call's (vgx_frontier_ms)
+};
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
 // Only integer atomics write it, one accumulate call at a time (vg_ctx::change_mu of the owner).
@@ -654,6 +668,7 @@ struct vg_ctx {
   vg::OccBufs occ;           // vg_occupancy staging and count planes (occupancy.hip), allocated on first use
   vg::ClrBufs clr;           // vg_clearance staging and planes (clearance.hip), allocated on first use
   vg::NavBufs nav;           // vg_navfn / vg_nav_paths planes (navfn.hip), allocated on first use
+  vg::FrontierBufs fr;       // vg_frontiers planes (frontier.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -1074,6 +1089,12 @@ int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const 
               int n_goals, uint32_t* pot, vg_nav_summary* out);
 int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
                   int32_t* status, int64_t* path_cost);
+// frontier.hip: the frontiers of an nx x ny grid (host grid and cost in, or null: the planes the last vg_occupancy /
+// vg_clearance left on the device; with flags bit 1 NavBufs::pot is read; labels (or null), the first max_records
+// records and the summary out); synchronous on the context stream, which the caller drained. Arguments: checked
+// by the caller
+int frontiers_dev(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm, int32_t* labels,
+                  vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 int change_clear_dev(vg_ctx* ctx, ChangeLayer* L);
@@ -1115,6 +1136,9 @@ int host_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const
                int n_goals, uint32_t* pot, vg_nav_summary* out);
 int host_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
                    int32_t* status, int64_t* path_cost);
+// frontier_host.cpp: the call behind the C-ABI
+int host_frontiers(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm, int32_t* labels,
+                   vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

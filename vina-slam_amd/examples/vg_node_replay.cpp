@@ -17,7 +17,7 @@
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
 //         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
 //          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]
-//           [--plan "gx gy" [--from "sx sy"] --path out.csv]]]]
+//           [--plan "gx gy" [--from "sx sy"] --path out.csv] [--frontiers out.csv]]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
@@ -65,6 +65,11 @@
 // world point gx gy, and the path down it from the cell holding --from "sx sy" (default: the last pose), written
 // to --path out.csv as one x,y,pot row per cell (the cell's centre in metres, its cost-to-go), the start first.
 // One line on stdout: the status (REACHED, NO_PATH, TRUNCATED, STUCK), the number of cells and the start's cost.
+// --frontiers out.csv (with --costmap): the exploration frontiers of that grid over that costmap, both where they
+// lie on the device (NodeCore::frontiers: vg_frontiers with grid == NULL and cost == NULL), with --plan only those
+// the plan's field reaches, ranked by it. One label,size,cx,cy,best_x,best_y,best_pot row per frontier in the
+// order to visit them (cx, cy: the world centroid; best_x, best_y: the cheapest cell's centre, nan without
+// --plan), and one line on stdout: frontiers: N kept of M, K cells.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -78,7 +83,7 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
   std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix, plan_s, from_s,
-      plan_csv;
+      plan_csv, fr_csv;
   double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0;
   int ck_at = -1;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
@@ -100,6 +105,7 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--plan") plan_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--from") from_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--path") plan_csv = argv0[++i];
+    else if (i + 1 < argc0 && a == "--frontiers") fr_csv = argv0[++i];
     else if (i + 1 < argc0 && a == "--inscribed") cm_inscribed = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--inflation") cm_inflation = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--cost-scaling") cm_scaling = atof(argv0[++i]);
@@ -129,6 +135,10 @@ int main(int argc0, char** argv0) {
       (cm_prefix.empty() || plan_csv.empty() || sscanf(plan_s.c_str(), "%lf %lf", &plan_goal[0], &plan_goal[1]) != 2 ||
        (!from_s.empty() && sscanf(from_s.c_str(), "%lf %lf", &plan_from[0], &plan_from[1]) != 2))) {
     fprintf(stderr, "%s: --plan \"gx gy\" needs --costmap CPREFIX and --path FILE; --from is \"sx sy\"\n", argv0[0]);
+    return 2;
+  }
+  if (!fr_csv.empty() && cm_prefix.empty()) {
+    fprintf(stderr, "%s: --frontiers FILE needs --costmap CPREFIX\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -443,6 +453,28 @@ int main(int argc0, char** argv0) {
           printf("plan: %s, %d cells, cost %lld, from %.17g %.17g to %.17g %.17g; %lld of %lld passable cells reached\n",
                  names[pl.status & 3], (int)pl.cells.size(), (long long)pl.cost, plan_from[0], plan_from[1], plan_goal[0],
                  plan_goal[1], (long long)pl.summary.cells_reached, (long long)pl.summary.cells_passable);
+        }
+        if (!fr_csv.empty()) {
+          const vina_gpu::LioCore::Frontiers fs = node.frontiers(!plan_s.empty());
+          FILE* ff = fopen(fr_csv.c_str(), "w");
+          if (!ff) {
+            perror("frontiers");
+            return 1;
+          }
+          for (const int k : fs.order()) {
+            const vg_frontier_rec& r = fs.recs[(size_t)k];
+            double best[2] = {NAN, NAN};
+            if (r.best_cell >= 0) node.cell_xy(r.best_cell, best);
+            fprintf(ff, "%d,%d,%.17g,%.17g,%.17g,%.17g,%u\n", r.label, r.size,
+                    cm.x0 + ((double)r.sum_x / r.size + 0.5) * cm.res, cm.y0 + ((double)r.sum_y / r.size + 0.5) * cm.res,
+                    best[0], best[1], r.best_pot);
+          }
+          if (fclose(ff) != 0) {
+            perror("frontiers");
+            return 1;
+          }
+          printf("frontiers: %lld kept of %lld, %lld cells\n", (long long)fs.summary.n_kept,
+                 (long long)fs.summary.n_components, (long long)fs.summary.n_frontier_cells);
         }
       }
       if (!occ_rays.empty()) {

@@ -178,6 +178,31 @@ class NavSummary(ctypes.Structure):
                 ("rounds", ctypes.c_int64), ("tile_runs", ctypes.c_int64), ("reserved", ctypes.c_int64 * 8)]
 
 
+class FrontierParams(ctypes.Structure):
+    """vg_frontier_params, 56 bytes."""
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("flags", ctypes.c_int), ("cost_max", ctypes.c_int),
+                ("min_size", ctypes.c_int), ("pad", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class FrontierRec(ctypes.Structure):
+    """vg_frontier_rec, 64 bytes (FRONTIER_REC is the same layout as a numpy dtype)."""
+    _fields_ = [("label", ctypes.c_int32), ("size", ctypes.c_int32), ("x_min", ctypes.c_int32), ("y_min", ctypes.c_int32),
+                ("x_max", ctypes.c_int32), ("y_max", ctypes.c_int32), ("sum_x", ctypes.c_int64), ("sum_y", ctypes.c_int64),
+                ("best_cell", ctypes.c_int32), ("best_pot", ctypes.c_uint32), ("reserved", ctypes.c_int64 * 2)]
+
+
+class FrontierSummary(ctypes.Structure):
+    """vg_frontier_summary, 128 bytes."""
+    _fields_ = [("n_frontier_cells", ctypes.c_int64), ("n_components", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_written", ctypes.c_int64), ("max_size", ctypes.c_int64), ("cells_free", ctypes.c_int64),
+                ("cells_unknown", ctypes.c_int64), ("n_rejected_cost", ctypes.c_int64),
+                ("n_rejected_unreached", ctypes.c_int64), ("reserved", ctypes.c_int64 * 7)]
+
+
+FRONTIER_REC = np.dtype([("label", "<i4"), ("size", "<i4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_max", "<i4"),
+                         ("y_max", "<i4"), ("sum_x", "<i8"), ("sum_y", "<i8"), ("best_cell", "<i4"), ("best_pot", "<u4"),
+                         ("reserved", "<i8", (2,))])
+FRONTIER_MAX_RECORDS = 65536
 NAV_SAT, NAV_UNREACHED = 0xFFFFFFFE, 0xFFFFFFFF
 NAV_K_ORTHO, NAV_K_DIAG = 12, 17
 NAV_MAX_POINTS, NAV_MAX_PATH_CELLS = 65536, 1 << 27
@@ -264,6 +289,16 @@ def nav_trav_table(flags=0, neutral=0, lethal_from=0, unknown_as=0, factor=0.0):
     if flags & 1:
         t[255] = t[unknown_as]
     return np.array(t, dtype=np.uint16)
+
+
+def frontier_order(recs):
+    """The indices of the frontier records (FRONTIER_REC) in the order to visit them: with best_cell >= 0 (the
+    reach test was on) by ascending (best_pot, label), the cheapest to drive to first; otherwise by descending
+    size, then ascending label."""
+    r = np.asarray(recs)
+    if r.size and (r["best_cell"] >= 0).all():
+        return np.lexsort((r["label"], r["best_pot"]))
+    return np.lexsort((r["label"], -r["size"].astype(np.int64)))
 
 
 def cells_to_world(cells, nx, x0, y0, res):
@@ -577,6 +612,12 @@ def lib():
             L.vg_navfn.argtypes = [P, P, ctypes.POINTER(NavParams), P, P, ctypes.c_int, P, ctypes.POINTER(NavSummary)]
             L.vg_nav_paths.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P]
             L.vgx_nav_ms.argtypes = [P, dp]
+        L.has_frontiers = hasattr(L, "vg_frontiers")  # a build older than the exploration frontiers (A/B runs)
+        if L.has_frontiers:
+            L.vg_frontiers.argtypes = [P, P, P, ctypes.POINTER(FrontierParams), P, P, ctypes.c_int,
+                                       ctypes.POINTER(FrontierSummary)]
+            L.vgx_frontier_ms.argtypes = [P, dp]
+            L.vgx_frontier_combine.argtypes = [P, ctypes.c_int]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -1089,6 +1130,50 @@ class Context:
         """Device time (ms) of the last navfn() or nav_paths() call's kernels."""
         ms = ctypes.c_double(0)
         self._chk(lib().vgx_nav_ms(self.h, ctypes.byref(ms)), "vgx_nav_ms")
+        return ms.value
+
+    # ---- exploration frontiers (vina_gpu.h "Exploration frontiers")
+    def frontiers(self, grid=None, *, nx=None, ny=None, cost=None, use_cost=False, use_pot=False, cost_max=0,
+                  min_size=0, max_records=4096, want_labels=True):
+        """vg_frontiers of grid (int8 [ny, nx] of OCC_*; None: the grid the last occupancy() call on this context
+        left on the device, nx and ny naming its shape). use_cost: only cells with cost < cost_max (0: 253), cost a
+        uint8 [ny, nx] plane or None: the one the last clearance() call left on the device (giving cost implies
+        use_cost). use_pot: only cells the field of the last navfn() call reaches; the records then carry the
+        cheapest cell. Returns (labels int32 [ny, nx], -1 off the frontier, or None without want_labels; the
+        records of the components with size >= min_size as a FRONTIER_REC array in ascending label, at most
+        max_records; the summary as a dict)."""
+        if not lib().has_frontiers:
+            raise VgError("this libvina_gpu.so has no exploration frontiers (vg_frontiers): rebuild it")
+        g = c = None
+        if grid is not None:
+            g = np.ascontiguousarray(grid, dtype=np.int8)
+            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
+                raise ValueError("frontiers: grid is [ny, nx]")
+            ny, nx = g.shape
+        elif nx is None or ny is None:
+            raise ValueError("frontiers: grid=None needs nx and ny")
+        if cost is not None:
+            c = np.ascontiguousarray(cost, dtype=np.uint8)
+            if c.shape != (ny, nx):
+                raise ValueError("frontiers: cost is [ny, nx]")
+            use_cost = True
+        p = FrontierParams()
+        p.nx, p.ny, p.flags = int(nx), int(ny), (1 if use_cost else 0) | (2 if use_pot else 0)
+        p.cost_max, p.min_size = cost_max, min_size
+        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        labels = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.int32) if want_labels else None
+        m = int(max_records)
+        recs = np.zeros(min(max(m, 0), FRONTIER_MAX_RECORDS), dtype=FRONTIER_REC)
+        s = FrontierSummary()
+        self._chk(lib().vg_frontiers(self.h, None if g is None else g.ctypes.data, None if c is None else c.ctypes.data,
+                                     ctypes.byref(p), None if labels is None else labels.ctypes.data,
+                                     recs.ctypes.data if recs.size else None, m, ctypes.byref(s)), "vg_frontiers")
+        return labels, recs[:s.n_written], {f: int(getattr(s, f)) for f, _ in FrontierSummary._fields_ if f != "reserved"}
+
+    def frontiers_ms(self):
+        """Device time (ms) of the last frontiers() call's kernels."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_frontier_ms(self.h, ctypes.byref(ms)), "vgx_frontier_ms")
         return ms.value
 
     # ---- the change layer (vina_gpu.h "Change layer")
