@@ -891,11 +891,13 @@ int LI_BA_Optimizer::damping_iter(std::vector<IMUST>& xs, LidarFactor& vox, std:
   std::vector<IMUST> xs_temp = xs;
   const int max_iter = 10;
   int it = 0;
+  n_hess = 0;
   MatX Hcalc;
   std::vector<double> Jcalc;
   for (int i = 0; i < max_iter; i++) {
     it++;
     if (is_calc_hess) {
+      n_hess++;
       residual1 = divide_thread(xs, vox, imus, Hess, JacT);
       Hcalc = Hess;
       Jcalc = JacT;

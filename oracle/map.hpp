@@ -219,6 +219,7 @@ struct LI_BA_Optimizer {
                        std::vector<double>& JacT);
   double only_residual(std::vector<IMUST>& xs, LidarFactor& vox, std::vector<IMU_PRE*>& imus);
   int damping_iter(std::vector<IMUST>& xs, LidarFactor& vox, std::vector<IMU_PRE*>& imus);
+  int n_hess = 0;  // divide_thread passes of the last damping_iter (its iterations minus the retries of rejected steps)
 };
 
 // LI_BA_OptimizerGravity — optimizers.cpp:629-826 (initialisation only): the

@@ -20,7 +20,8 @@ class Stats(ctypes.Structure):
                 ("iekf_matches", ctypes.c_int * 4), ("roots_new", ctypes.c_int), ("n_slide", ctypes.c_int),
                 ("n_factors", ctypes.c_int), ("ba_iters", ctypes.c_int), ("degenerate", ctypes.c_int),
                 ("plane_updates", ctypes.c_int), ("fix_full", ctypes.c_int), ("init_phase", ctypes.c_int),
-                ("init_rounds", ctypes.c_int), ("init_valid", ctypes.c_int)]
+                ("init_rounds", ctypes.c_int), ("init_valid", ctypes.c_int),
+                ("ba_hess", ctypes.c_int)]
 
 
 # int (*)(double* buf, int n, void* user): in-place sum over the ranks

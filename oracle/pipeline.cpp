@@ -638,6 +638,7 @@ struct Pipeline {
       opt.mpar = &mpar;
       opt.use_threads = cfg.use_threads != 0;
       st.ba_iters = opt.damping_iter(x_buf, voxhess, imu_pre_buf);
+      st.ba_hess = opt.n_hess;
     }
     x_curr.R = x_buf[win_count - 1].R;
     x_curr.p = x_buf[win_count - 1].p;

@@ -48,6 +48,7 @@ typedef struct orc_stats {
                        4 motion_init failed (system_reset) */
   int init_rounds;  /* motion_init rounds run on this scan */
   int init_valid;   /* init-window scan: kd-tree LIO correspondences (-1 = map seeded) */
+  int ba_hess;      /* Hessian passes of the scan's LM run (ba_iters - ba_hess: retries of rejected steps) */
 } orc_stats;
 
 void orc_voxel_key_d(const double* xyz, int n, double size, int64_t* out);

@@ -134,6 +134,9 @@ def check_case(cfgname, lidar, nscan, orc, gpu, so, sg):
         # margi's pcr_fix.N >= max_points branch (octree.cpp:461-469) and the LM were exercised
         assert sum(s["fix_full"] for s in sg) > 0
         assert min(s["ba_iters"] for s in sg[W - 1:]) > 0
+        # Hessian passes per scan (the oracle's divide_thread count): ba_iters - ba_hess steps were
+        # rejected and retried. No suite workload rejects one (tests/test_ba_step_gpu.py lists the counts)
+        assert [s["ba_hess"] for s in sg] == [s["ba_hess"] for s in so]
     gpu.close()
     orc.close()
 

@@ -600,11 +600,13 @@ __global__ void __launch_bounds__(256) k_ba_prep(int W, int nimu, double imu_coe
   }
   constexpr int kN = kMaxNB * kTile;
   __shared__ double Dv[kN], Jg[kN];
-  __shared__ int ip[kN];
+  __shared__ int ip[kN], perm[kN];
+  __shared__ int s_tie;
   const int n = 15 * W, L = 6 * W, m = n - 15, NB = (m + kTile - 1) / kTile, N = NB * kTile;
   const int tid = threadIdx.x, q = blockIdx.x;
   const bool calc = st->calc_hess != 0;
   const double u = st->u;
+  if (tid == 0) s_tie = 0;
   for (int t = tid; t < n; t += blockDim.x)
     Dv[t] = t < 15 ? 1.0 : (calc ? asm_entry(t, t, nimu, imu_coef, hl, imuout, L) : Hcalc[lo(t, t)]);
   __syncthreads();
@@ -614,16 +616,45 @@ __global__ void __launch_bounds__(256) k_ba_prep(int W, int nimu, double imu_coe
       ip[v >= 6 ? 9 * (j - 1) + (v - 6) : 9 * (W - 1) + 6 * (j - 1) + v] = i;
       continue;
     }
-    // Eigen's order: rank of |D + u D| descending, index ascending on ties
+    // Eigen's order: rank of |D + u D| descending (equal entries: below)
     const unsigned long long ki = (unsigned long long)__double_as_longlong(fabs(Dv[i] + u * Dv[i]));
-    int c = 0;
+    int c = 0, tie = 0;
     for (int j = 15; j < n; j++) {
       const unsigned long long kj = (unsigned long long)__double_as_longlong(fabs(Dv[j] + u * Dv[j]));
-      c += (kj > ki) || (kj == ki && j < i);
+      c += kj > ki;
+      tie |= (kj == ki && j != i);
     }
     ip[c] = i;
+    if (tie) s_tie = 1;
   }
   __syncthreads();
+  // Equal entries: Eigen takes the first largest of the remaining positions
+  // and transposes it with position k, so which of two equal entries comes
+  // first depends on the transpositions before (the gauge frame's 1 + u among
+  // them). Rare (exact fp64 equality): one lane replays the selection over all
+  // n entries and keeps the order of the factored ones.
+  if (!structural && s_tie) {
+    if (tid == 0) {
+      for (int t = 0; t < n; t++) perm[t] = t;
+      int o = 0;
+      for (int k = 0; k < n; k++) {
+        int p = k;
+        double best = fabs(Dv[perm[k]] + u * Dv[perm[k]]);
+        for (int i = k + 1; i < n; i++) {
+          const double a = fabs(Dv[perm[i]] + u * Dv[perm[i]]);
+          if (a > best) {
+            best = a;
+            p = i;
+          }
+        }
+        const int e = perm[p];
+        perm[p] = perm[k];
+        perm[k] = e;
+        if (e >= 15) ip[o++] = e;
+      }
+    }
+    __syncthreads();
+  }
   int TI = 0;
   while ((TI + 1) * (TI + 2) / 2 <= q) TI++;
   const int TJ = q - TI * (TI + 1) / 2;
@@ -1642,6 +1673,22 @@ struct InitHessArg {
   int fin;
   int seq0;  // > 0: the LM's first flag number (a direct launch); 0: DState::ph (the scan graph)
 };
+// k_ba_prep then k_ba_solve of one LM iteration on the system in `hlx` /
+// d.imuout (ba_iter_kernels, and the test entry ba_step_test); ev: the event
+// pair around k_ba_solve (vg_profile), or nullptr
+static void launch_prep_solve(vg_ctx* ctx, const BaDev& d, const double* hlx, int xworld, hipEvent_t* ev) {
+  const int W = ctx->cfg.win_size, nimu = W - 1;
+  hipStream_t s = ctx->stream;
+  const int NBt = (15 * W - 15 + kTile - 1) / kTile, ntile = NBt * (NBt + 1) / 2;
+  k_ba_prep<<<ntile, 256, 0, s>>>(W, nimu, ctx->cfg.imu_coef, hlx, d.imuout, d.Hcalc, d.Jcalc, d.timg, d.bvec,
+                                  d.dvec, d.jvec, d.ipg, d.st, ctx->ba_structural ? 1 : 0, xworld,
+                                  ctx->map.counters + kCntErr);
+  if (ev) (void)hipEventRecord(ev[0], s);
+  k_ba_solve<<<1, 1024, solve_lds_bytes(W), s>>>(W, nimu, d.timg, d.bvec, d.dvec, d.jvec, d.ipg, d.xs, d.xt, d.bias,
+                                                 d.dxi, d.st, &ctx->st->clk);
+  if (ev) (void)hipEventRecord(ev[1], s);
+}
+
 static void ba_iter_kernels(vg_ctx* ctx, int k, bool solve_ev, int& xerr, int rh = 0,
                             const InitHessArg* ih = nullptr) {
   const int W = ctx->cfg.win_size;
@@ -1656,8 +1703,6 @@ static void ba_iter_kernels(vg_ctx* ctx, int k, bool solve_ev, int& xerr, int rh
   const int G = std::min(kHessGridMax, ctx->ba.cap_f / hess_chunk(W) + 1);
   const int nrb = kResidBlocks;
   const size_t hess_lds = hess_lds_bytes(W);
-  const size_t solve_lds = solve_lds_bytes(W);
-  const int NBt = (15 * W - 15 + kTile - 1) / kTile, ntile = NBt * (NBt + 1) / 2;
   Shard& sh = ctx->shard;
   // sharded: the Hessian / gradient / residual frame and the trial residual's
   // frame are packed by k_ba_hfinal / k_ba_rsum and checked by k_ba_prep /
@@ -1690,13 +1735,7 @@ static void ba_iter_kernels(vg_ctx* ctx, int k, bool solve_ev, int& xerr, int rh
     ctx->dbg_cap_n = nout + nimu * 931;
     ctx->dbg_capture = 2;
   }
-  k_ba_prep<<<ntile, 256, 0, s>>>(W, nimu, ctx->cfg.imu_coef, hlx, d.imuout, d.Hcalc, d.Jcalc, d.timg, d.bvec,
-                                  d.dvec, d.jvec, d.ipg, d.st, ctx->ba_structural ? 1 : 0, shard_on ? sh.world : 0,
-                                  ctx->map.counters + kCntErr);
-  if (solve_ev) (void)hipEventRecord(ctx->solve_ev[k][0], s);
-  k_ba_solve<<<1, 1024, solve_lds, s>>>(W, nimu, d.timg, d.bvec, d.dvec, d.jvec, d.ipg, d.xs, d.xt, d.bias, d.dxi,
-                                       d.st, &ctx->st->clk);
-  if (solve_ev) (void)hipEventRecord(ctx->solve_ev[k][1], s);
+  launch_prep_solve(ctx, d, hlx, shard_on ? sh.world : 0, solve_ev ? ctx->solve_ev[k] : nullptr);
   if (rh == 1)
     k_ba_resid_hess<<<kRhChunkWg + 1 + nimu, kHessThreads, hess_lds, s>>>(
         nfp, W, ctx->ba.fac_node, ctx->map.pcr_fix, ctx->map.pcrs, d.mpring, d.xt, ctx->ba.fac_eig, ctx->ba.fac_pcr,
@@ -2053,6 +2092,105 @@ int ba_solve_test(vg_ctx* ctx, const double* A, const double* b, double* x) {
   VG_HIP(hipMemcpyAsync(out.data(), d.dxi, n * sizeof(double), hipMemcpyDeviceToHost, s));
   VG_HIP(hipStreamSynchronize(s));
   for (int t = 0; t < m; t++) x[t] = out[15 + t];
+  return VG_OK;
+}
+
+// Test-only (vgx_ba_step): one LM step's k_ba_prep + k_ba_solve, launched as
+// ba_iter_kernels launches them (launch_prep_solve), on a given LiDAR system
+// hl (packed lower 6W x 6W, 6W gradient, residual), IMU blocks imuout
+// ((W-1) x 931), window states xs (W x 24), bias records (W-1) x 12 and the LM
+// state's u, v, calc_hess. The stored system (Hcalc / Jcalc) stays on the
+// device between calls, so a calc_hess = 0 call re-reads what the previous
+// call stored. The window states and bias records are the context's own: use
+// a context that is not stepped afterwards.
+int ba_step_test(vg_ctx* ctx, const double* hl, const double* imuout, const double* xs, const double* bias, double u,
+                 double v, int calc_hess, double* dxi, double* xt, double* bias_out, double* q1_res1, int* ipg,
+                 double* Hcalc, double* Jcalc) {
+  const int W = ctx->cfg.win_size, n = 15 * W, m = n - 15, nimu = W - 1;
+  const int L = 6 * W, nout = L * (L + 1) / 2 + L + 1, nn = n * (n + 1) / 2;
+  if (sharded(ctx)) return VG_E_STATE;
+  hipStream_t s = ctx->stream;
+  BaDev d = carve(ctx);
+  BaState bs;
+  memset(&bs, 0, sizeof(bs));
+  bs.u = u;
+  bs.v = v;
+  bs.calc_hess = calc_hess;
+  VG_HIP(hipMemcpyAsync(d.hl, hl, (size_t)nout * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.imuout, imuout, (size_t)nimu * 931 * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.xs, xs, (size_t)W * kX * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.bias, bias, (size_t)nimu * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.st, &bs, sizeof(bs), hipMemcpyHostToDevice, s));
+  VG_HIP(hipStreamSynchronize(s));
+  launch_prep_solve(ctx, d, d.hl, 0, nullptr);
+  VG_HIP(hipGetLastError());
+  std::vector<int> ipv(kMaxNB * kTile);
+  VG_HIP(hipMemcpyAsync(dxi, d.dxi, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(xt, d.xt, (size_t)W * kX * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(bias_out, d.bias, (size_t)nimu * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(&bs, d.st, sizeof(bs), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(ipv.data(), d.ipg, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(Hcalc, d.Hcalc, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(Jcalc, d.Jcalc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipStreamSynchronize(s));
+  q1_res1[0] = bs.q1;
+  q1_res1[1] = bs.res1;
+  for (int t = 0; t < m; t++) ipg[t] = ipv[t];
+  return VG_OK;
+}
+
+// Test-only (vgx_ba_control): one k_ba_control launch (the LM bookkeeping,
+// ba_control_body) on a given LM state — sd: u, v, res1, res2, q1; si:
+// calc_hess, done, iters, nhess, fin, skip — the IMU residuals imures (W-1),
+// nrb <= kResidBlocks residual partials, the window states xs, the trial
+// states xt and the bias records. Returns the state, xs and the bias records
+// after the launch. The context must not be stepped afterwards.
+int ba_control_test(vg_ctx* ctx, double* sd, int* si, const double* imures, const double* rpart, int nrb, double* xs,
+                    const double* xt, double* bias) {
+  const int W = ctx->cfg.win_size, nimu = W - 1, L = 6 * W, nl = L * (L + 1) / 2;
+  if (sharded(ctx)) return VG_E_STATE;
+  if (nrb < 0 || nrb > kResidBlocks) return VG_E_ARG;
+  hipStream_t s = ctx->stream;
+  BaDev d = carve(ctx);
+  BaState bs;
+  memset(&bs, 0, sizeof(bs));
+  bs.u = sd[0];
+  bs.v = sd[1];
+  bs.res1 = sd[2];
+  bs.res2 = sd[3];
+  bs.q1 = sd[4];
+  bs.calc_hess = si[0];
+  bs.done = si[1];
+  bs.iters = si[2];
+  bs.nhess = si[3];
+  bs.fin = si[4];
+  bs.skip = si[5];
+  VG_HIP(hipMemcpyAsync(d.st, &bs, sizeof(bs), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.imures, imures, (size_t)nimu * sizeof(double), hipMemcpyHostToDevice, s));
+  if (nrb > 0) VG_HIP(hipMemcpyAsync(d.rpart, rpart, (size_t)nrb * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.xs, xs, (size_t)W * kX * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.xt, xt, (size_t)W * kX * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(d.bias, bias, (size_t)nimu * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+  VG_HIP(hipStreamSynchronize(s));
+  CtlArg ctl{W, nimu, nrb, nl + L, ctx->cfg.imu_coef, d.hl, d.imuout, d.imures, d.rpart, d.xs, d.xt, d.bias, d.st,
+             ctx->d_pub, nullptr, 0, ctx->map.counters + kCntErr};
+  k_ba_control<<<1, 256, 0, s>>>(ctl);
+  VG_HIP(hipGetLastError());
+  VG_HIP(hipMemcpyAsync(&bs, d.st, sizeof(bs), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(xs, d.xs, (size_t)W * kX * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipMemcpyAsync(bias, d.bias, (size_t)nimu * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+  VG_HIP(hipStreamSynchronize(s));
+  sd[0] = bs.u;
+  sd[1] = bs.v;
+  sd[2] = bs.res1;
+  sd[3] = bs.res2;
+  sd[4] = bs.q1;
+  si[0] = bs.calc_hess;
+  si[1] = bs.done;
+  si[2] = bs.iters;
+  si[3] = bs.nhess;
+  si[4] = bs.fin;
+  si[5] = bs.skip;
   return VG_OK;
 }
 

@@ -981,6 +981,11 @@ const int* ba_hess_dev(vg_ctx* ctx);  // Hessian passes of the last LM run (I_H 
 int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_ring, double* out);
 int ba_factor_normals(vg_ctx* ctx, std::vector<double>& normals);
 int ba_solve_test(vg_ctx* ctx, const double* A, const double* b, double* x);  // vgx_ba_solve  // column 0 of each factor's eigenvectors
+int ba_step_test(vg_ctx* ctx, const double* hl, const double* imuout, const double* xs, const double* bias, double u,
+                 double v, int calc_hess, double* dxi, double* xt, double* bias_out, double* q1_res1, int* ipg,
+                 double* Hcalc, double* Jcalc);  // vgx_ba_step
+int ba_control_test(vg_ctx* ctx, double* sd, int* si, const double* imures, const double* rpart, int nrb, double* xs,
+                    const double* xt, double* bias);  // vgx_ba_control
 // host_mirror.cpp: the host mirror's lifetime, absorption and accessors
 // (host_sync, host_stats_log below as well)
 void host_init(vg_ctx* ctx);

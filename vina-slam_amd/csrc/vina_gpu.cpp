@@ -1220,6 +1220,42 @@ extern "C" int vgx_ba_solve(vg_ctx* ctx, const double* A, const double* b, doubl
   return vg::ba_solve_test(ctx, A, b, x);
 }
 
+// Test-only: one LM step between the Hessian pass and the residual pass —
+// k_ba_prep then k_ba_solve as an LM iteration launches them — on a given
+// LiDAR system hl (packed lower 6W x 6W, 6W gradient, residual), IMU blocks
+// imuout ((W-1) x 931), window states xs (W x 24), bias records ((W-1) x 12)
+// and u, v, calc_hess. Out: dxi (15W), xt (W x 24), the bias records, q1 and
+// res1 (q1_res1[2]), the pivot order ipg (15W - 15), the stored system Hcalc
+// (packed lower 15W x 15W) and Jcalc (15W). A calc_hess = 0 call re-reads the
+// system the previous call stored. The context must not be stepped after.
+extern "C" int vgx_ba_step(vg_ctx* ctx, const double* hl, const double* imuout, const double* xs, const double* bias,
+                           double u, double v, int calc_hess, double* dxi, double* xt, double* bias_out,
+                           double* q1_res1, int* ipg, double* Hcalc, double* Jcalc) {
+  if (!ctx || !hl || !imuout || !xs || !bias || !dxi || !xt || !bias_out || !q1_res1 || !ipg || !Hcalc || !Jcalc)
+    return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  return vg::ba_step_test(ctx, hl, imuout, xs, bias, u, v, calc_hess, dxi, xt, bias_out, q1_res1, ipg, Hcalc, Jcalc);
+}
+
+// Test-only: one k_ba_control launch (the LM's accept / reject bookkeeping) on
+// a given state — sd[5]: u, v, res1, res2, q1; si[6]: calc_hess, done, iters,
+// nhess, fin, skip — with the IMU residuals imures (W-1), nrb residual
+// partials (at most k_ba_resid's workgroup count, else VG_E_ARG), xs, xt
+// (W x 24) and the bias records. sd, si, xs and bias are updated in place;
+// *accept = 1 accepted, 0 rejected, -1 the LM had already ended (read from the
+// state: a live launch leaves calc_hess = 1 exactly when it accepts). The
+// unsharded product path runs the same bookkeeping inside k_ba_resid. The
+// context must not be stepped after.
+extern "C" int vgx_ba_control(vg_ctx* ctx, double* sd, int* si, const double* imures, const double* rpart, int nrb,
+                              double* xs, const double* xt, double* bias, int* accept) {
+  if (!ctx || !sd || !si || !imures || (!rpart && nrb > 0) || !xs || !xt || !bias || !accept) return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  const int done_before = si[1];
+  VG_TRY(vg::ba_control_test(ctx, sd, si, imures, rpart, nrb, xs, xt, bias));
+  *accept = done_before ? -1 : (si[0] ? 1 : 0);
+  return VG_OK;
+}
+
 // Test-only: one k_iekf_update launch on given sums (iekf.hip iekf_update_test:
 // nb >= 0 block partials through the ordered reduction, nb < 0 the 34 final
 // sums). G6_out holds 96 doubles (G6 15 x 6, then nnt). The context must not be

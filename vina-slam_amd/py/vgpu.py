@@ -684,6 +684,10 @@ def lib():
         L.vgx_ba_capture.argtypes = [P, dp, ctypes.c_int, ip]
         if hasattr(L, "vgx_ba_solve"):  # absent from builds older than the test entry (A/B runs)
             L.vgx_ba_solve.argtypes = [P, dp, dp, dp]
+        if hasattr(L, "vgx_ba_step"):
+            L.vgx_ba_step.argtypes = [P, dp, dp, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, dp, dp, dp,
+                                      dp, ip, dp, dp]
+            L.vgx_ba_control.argtypes = [P, dp, ip, dp, dp, ctypes.c_int, dp, dp, dp, ip]
         if hasattr(L, "vgx_memo_probe"):
             L.vgx_memo_probe.argtypes = [P, ip]
         if hasattr(L, "vgx_map_nodes"):
@@ -1603,6 +1607,53 @@ class Context:
         x = np.zeros(b.shape[0])
         self._chk(lib().vgx_ba_solve(self.h, _d(A), _d(b), _d(x)), "vgx_ba_solve")
         return x
+
+    def ba_step(self, W, hl, imuout, xs, bias, u, v=2.0, calc_hess=1):
+        """One LM step's k_ba_prep + k_ba_solve (vgx_ba_step) on the LiDAR system hl (packed lower
+        6W x 6W, 6W gradient, residual), the IMU blocks imuout (W-1, 931), the window states xs
+        (W, 24) and the bias records (W-1, 12). W is the context's win_size. Returns a dict: dxi,
+        xt, bias, q1, res1, ipg, Hcalc (packed lower 15W x 15W), Jcalc. The context must not be
+        stepped afterwards."""
+        n, L = 15 * W, 6 * W
+        hl = np.ascontiguousarray(hl, dtype=np.float64)
+        imuout = np.ascontiguousarray(imuout, dtype=np.float64)
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        bias = np.ascontiguousarray(bias, dtype=np.float64)
+        assert hl.size == L * (L + 1) // 2 + L + 1 and imuout.size == (W - 1) * 931
+        assert xs.size == W * 24 and bias.size == (W - 1) * 12
+        o = {"dxi": np.zeros(n), "xt": np.zeros((W, 24)), "bias": np.zeros((W - 1, 12)),
+             "ipg": np.zeros(n - 15, dtype=np.int32), "Hcalc": np.zeros(n * (n + 1) // 2), "Jcalc": np.zeros(n)}
+        qr = np.zeros(2)
+        self._chk(lib().vgx_ba_step(self.h, _d(hl), _d(imuout), _d(xs), _d(bias), u, v, calc_hess, _d(o["dxi"]),
+                                    _d(o["xt"]), _d(o["bias"]), _d(qr),
+                                    o["ipg"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _d(o["Hcalc"]),
+                                    _d(o["Jcalc"])), "vgx_ba_step")
+        o["q1"], o["res1"] = float(qr[0]), float(qr[1])
+        return o
+
+    BA_STATE_D = ("u", "v", "res1", "res2", "q1")
+    BA_STATE_I = ("calc_hess", "done", "iters", "nhess", "fin", "skip")
+
+    def ba_control(self, W, state, imures, rpart, xs, xt, bias):
+        """One k_ba_control launch (vgx_ba_control) on the LM state `state` (a dict over BA_STATE_D
+        and BA_STATE_I), the IMU residuals (W-1), the residual partials rpart, xs, xt (W, 24) and
+        the bias records (W-1, 12). Returns (state, xs, bias, accept) after the launch; accept is
+        1, 0, or -1 when the LM had already ended. The context must not be stepped afterwards."""
+        sd = np.array([state[k] for k in self.BA_STATE_D], dtype=np.float64)
+        si = np.array([state[k] for k in self.BA_STATE_I], dtype=np.int32)
+        imures = np.ascontiguousarray(imures, dtype=np.float64)
+        rpart = np.ascontiguousarray(rpart, dtype=np.float64)
+        xs = np.array(xs, dtype=np.float64).reshape(W, 24)
+        xt = np.ascontiguousarray(xt, dtype=np.float64)
+        bias = np.array(bias, dtype=np.float64).reshape(W - 1, 12)
+        assert imures.size == W - 1 and xt.size == W * 24
+        acc = ctypes.c_int(0)
+        ip = ctypes.POINTER(ctypes.c_int)
+        self._chk(lib().vgx_ba_control(self.h, _d(sd), si.ctypes.data_as(ip), _d(imures), _d(rpart), rpart.size,
+                                       _d(xs), _d(xt), _d(bias), ctypes.byref(acc)), "vgx_ba_control")
+        out = {k: float(sd[i]) for i, k in enumerate(self.BA_STATE_D)}
+        out.update({k: int(si[i]) for i, k in enumerate(self.BA_STATE_I)})
+        return out, xs, bias, acc.value
 
     LA_OPS = {"eig3": (0, 9, 12), "exp": (1, 3, 9), "exp_dt": (2, 4, 9), "log": (3, 9, 3), "jr": (4, 3, 9),
               "jr_inv": (5, 9, 9), "inverse6": (6, 36, 36), "inverse15": (7, 225, 225), "colpiv_qr": (8, 33, 3),
