@@ -40,7 +40,7 @@ PLANE_B = 224.0
 
 
 def hess_chunk(W):
-    """factors per k_ba_hess chunk (ba.hip hess_fs, kHessThreads = 512)"""
+    """factors per k_ba_hess chunk (vg_ba.h hess_fs, kHessThreads = 512)"""
     return 2 * (256 // W) if 2 * (256 // W) <= 64 and 2 * (256 // W) <= 512 // W else min(512 // W, 64)
 
 

@@ -8,7 +8,7 @@ mpmath; nothing here comes from oracle/ or from the device code.
 tests/test_lm_ref.py pins `solve` against the oracle's ldlt_solve and
 `assemble` against a brute-force accumulation.
 
-Layouts (the device's, csrc/ba.hip): hl = the 6W x 6W LiDAR Hessian as packed
+Layouts (the device's, csrc/ba_factor.hip, ba_solve.hip): hl = the 6W x 6W LiDAR Hessian as packed
 lower rows, then the 6W gradient, then the residual; imuout = (W-1) x 931, per
 IMU factor the 30 x 30 J^T C J (row-major), the 30 gradient entries, r^T C r;
 a frame's state = R 9 (row-major), p, v, bg, ba, g; a bias record = bg 3, ba 3,

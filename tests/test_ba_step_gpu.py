@@ -59,7 +59,7 @@ COEF = 2.0 ** -13
 U53 = 2.0 ** -53
 WINS = [2, 3, 10, 11]
 US = [0.01, 0.01 / 3, 1e3]
-RESID_BLOCKS = 512  # k_ba_resid's workgroup count (ba.hip kResidBlocks; test_control_rejects_too_many_partials)
+RESID_BLOCKS = 512  # k_ba_resid's workgroup count (vg_ba.h kResidBlocks; test_control_rejects_too_many_partials)
 
 _ctxs = {}
 

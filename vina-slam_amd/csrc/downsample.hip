@@ -847,16 +847,13 @@ int ds_enqueue_hashed(vg_ctx* ctx, hipStream_t s, const float* x, const float* y
       }
     };
     const bool use_graph = ctx->use_graphs && fallback && voxel == ctx->cfg.down_size;
-    if (use_graph && !ctx->g_ds) {
-      std::lock_guard<std::recursive_mutex> cap_lk_(capture_mutex());  // (vg_internal.h)
-      VG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      chain(s);
-      hipGraph_t gr = nullptr;
-      VG_HIP(hipStreamEndCapture(s, &gr));
-      VG_HIP(hipGraphInstantiate(&ctx->g_ds, gr, nullptr, nullptr, 0));
-      VG_HIP(hipGraphDestroy(gr));
+    if (use_graph) {
+      VG_TRY(capture_once(ctx, s, &ctx->g_ds, [&]() {
+        chain(s);
+        return VG_OK;
+      }));
+      VG_HIP(hipGraphLaunch(ctx->g_ds, s));
     }
-    if (use_graph) VG_HIP(hipGraphLaunch(ctx->g_ds, s));
     else chain(s);
   }
   if (pub_seq > 0) VG_TRY(state_publish_ds(ctx, s, pub_seq, d.hflags, false));

@@ -266,17 +266,7 @@ int iekf_run(vg_ctx* ctx, const MP& mp, const float* x, const float* y, const fl
     return VG_OK;
   }
   hipGraphExec_t& ge = ctx->g_iekf[self_signal ? 3 : 0];
-  if (!ge) {
-    std::lock_guard<std::recursive_mutex> cap_lk_(capture_mutex());  // (vg_internal.h)
-    VG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int r = enqueue();
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(s, &g);
-    if (r != VG_OK) return r;
-    VG_HIP(e);
-    VG_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    VG_HIP(hipGraphDestroy(g));
-  }
+  VG_TRY(capture_once(ctx, s, &ge, enqueue));
   VG_HIP(hipGraphLaunch(ge, s));
   if (signalled) *signalled = self_signal;
   return VG_OK;

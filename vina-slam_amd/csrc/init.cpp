@@ -15,7 +15,7 @@
 // motion_blur's per-point transform (state.hip k_blur_init), the map rebuild of
 // every round (insert.hip with precomputed body points, recut.hip with
 // the initialisation thresholds) and the LiDAR factor Hessian / residual
-// passes of the gravity LM (ba.hip). The host keeps what is O(IMU samples) or
+// passes of the gravity LM (ba_factor.hip). The host keeps what is O(IMU samples) or
 // O(window): the IMU means, the IMU pose integration, the preintegration, the
 // IMU factors with the gravity Jacobian, the (15W+3)-unknown LDLT of the 3 LM
 // iterations per round, align_gravity and the accept / convergence rules.

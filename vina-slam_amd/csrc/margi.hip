@@ -733,17 +733,7 @@ int map_margi(vg_ctx* ctx, const MP& mp, const WinArg& wa, int n_oldest, int thr
   (void)n_oldest;
   if (!ctx->use_graphs || ctx->prof_stages) return body();
   hipGraphExec_t& ge = ctx->g_margi[(gate ? 1 : 0) + (copy_signals ? 2 : 0)];
-  if (!ge) {
-    std::lock_guard<std::recursive_mutex> cap_lk_(capture_mutex());  // (vg_internal.h)
-    VG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int r = body();
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(s, &g);
-    if (r != VG_OK) return r;
-    VG_HIP(e);
-    VG_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    VG_HIP(hipGraphDestroy(g));
-  }
+  VG_TRY(capture_once(ctx, s, &ge, body));
   VG_HIP(hipGraphLaunch(ge, s));
   return VG_OK;  // device error flags reach the host with the end-of-scan counters
 }

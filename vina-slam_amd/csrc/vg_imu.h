@@ -1,6 +1,6 @@
 // vg_imu.h — IMU_PRE::give_evaluate's residual and Jacobian
 // (imu_preintegration.cpp:97-163) on a preintegration record, host and device:
-// the BA kernels (ba.hip) and the initialisation's gravity LM (init.cpp,
+// the BA kernels (ba_factor.hip) and the initialisation's gravity LM (init.cpp,
 // give_evaluate_g, imu_preintegration.cpp:165-237) evaluate the same code.
 #pragma once
 #include "vg_la.h"

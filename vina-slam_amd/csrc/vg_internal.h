@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/vina_gpu.h"
 #include "vg_la.h"
+#include "vg_lm_loop.h"  // BaLoop: an LM run's host loop state (vg_ctx::ba_loop)
 #include "vg_scratch.h"
 
 #define VG_HIP(call)                                                                    \
@@ -225,10 +226,10 @@ struct BaBufs {
   double* fac_eig = nullptr;   // trial eig values/vectors (12) per factor
   Clu* fac_pcr = nullptr;      // trial merged cluster per factor
   double* hpart = nullptr;     // chunk partials
-  double* hout = nullptr;      // reduced 60x60 upper + 60 + 1
+  double* hout = nullptr;      // reduced LiDAR system: 6W x 6W packed lower rows + 6W gradient + the residual
   double* hout_part = nullptr; // this shard's part of it (sharded mode)
   double* rpart = nullptr;
-  double* xs = nullptr;        // window poses (W x 12: R9 p3)
+  double* xs = nullptr;        // 1024 doubles of WinD / counts staging (map stages), then the LM's carved block (vg_ba.h carve)
 };
 
 // ---- device-resident estimator state (state.hip) ----
@@ -377,14 +378,6 @@ struct Pub {
   double traj[16];
   double nnt[8];
   double xs[kMaxWin * kXS];
-};
-// An LM run whose outcome the host has not read yet (ba_run's loop state,
-// continued by ba_resolve): the fused step returns once the LM iterations and
-// the speculative margi tail are enqueued, and the next step enqueues its
-// downsample, propagation and IEKF before it waits for that outcome
-struct BaLoop {
-  int seq0 = 0, enq = 0, tail_at = 0, k = 0;  // first iteration flag number, iterations enqueued, ahead of the tail, next k
-  bool active = false;
 };
 // The query-side scratch below is made of DevBuf / KernelTimer members
 // (vg_scratch.h): each buffer is reserved where it is first needed and freed by
@@ -945,8 +938,9 @@ int state_blur_init(vg_ctx* ctx, const double* par, int npose, const float4* pts
                     double* d_par, double* pnt);
 // window states / x_curr / IMU records (+ zero bias, ring head 0) -> DState; synchronous
 int state_load(vg_ctx* ctx, const double* xs, int nw, const double* xc, const double* recs, int nrec);
-// ba.hip
-constexpr int kBaX = 24;        // per-frame state: R 9, p 3, v 3, bg 3, ba 3, g 3
+// ba.hip (the driver), ba_factor.hip (ba_lidar_pass, ba_factor_normals,
+// ba_control_test), ba_solve.hip (ba_solve_test, ba_step_test)
+constexpr int kBaX = 24;       // per-frame state: R 9, p 3, v 3, bg 3, ba 3, g 3
 int ba_alloc(vg_ctx* ctx);
 // LM on the device state (window states, IMU_PRE records and bias records in
 // DState; the factor count in the map counters). Returns once the LM has
@@ -1024,6 +1018,27 @@ int dev_ctx_count(int device);
 // contexts (one-time work per context): the multi-sequence mode's worker
 // threads otherwise capture concurrently (B = 16: sixteen threads at once).
 std::recursive_mutex& capture_mutex();
+// Capture `body` (int(): VG_OK or an error) on `s` once and keep the
+// instantiated graph in *ge (a no-op once *ge is set). Holds capture_mutex();
+// the capture is thread-local and always ended; the body's error comes before
+// the capture's.
+template <class Body>
+int capture_once(vg_ctx* ctx, hipStream_t s, hipGraphExec_t* ge, Body&& body) {
+  if (*ge) return VG_OK;
+  std::lock_guard<std::recursive_mutex> cap_lk_(capture_mutex());
+  VG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int r = body();
+  hipGraph_t g = nullptr;
+  const hipError_t e = hipStreamEndCapture(s, &g);
+  if (r != VG_OK) {
+    if (e == hipSuccess && g) (void)hipGraphDestroy(g);
+    return r;
+  }
+  VG_HIP(e);
+  VG_HIP(hipGraphInstantiate(ge, g, nullptr, nullptr, 0));
+  VG_HIP(hipGraphDestroy(g));
+  return VG_OK;
+}
 void graphs_drop(vg_ctx* ctx);  // destroy every captured graph (vina_gpu.cpp): ctx->map is about to name other memory
 int host_release_far(vg_ctx* ctx, int flags, long long* out);
 bool host_release_pending(vg_ctx* ctx);  // jour advanced in an absorbed scan since the last release
