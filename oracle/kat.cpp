@@ -36,20 +36,19 @@ void orc_kat_p2p(const double* R9, const double* p3, const double* pnt3, const d
   for (int k = 0; k < 6; k++) j6[k] = jac[k];
 }
 
-// One LidarFactor voxel (factors.cpp:11-126): W local clusters (13 doubles
-// each: P 9, v 3, N), the fixed cluster, window poses (12 each: R 9, p 3).
-// The eigen system comes from the merged cluster at the given poses, as
-// tras_opt hands it over after a recut / residual pass. Outputs lambda_min,
-// JacT (6W) and the Hessian (6W x 6W, row-major). hess may be null.
-void orc_kat_lidar_factor(int W, const double* clu, const double* fix, const double* poses, double* res,
-                          double* jac, double* hess) {
-  std::vector<IMUST> xs(W);
+// evaluate_only_residual's merge for one voxel (factors.cpp:137-150): the
+// local clusters moved to the window poses and added onto the fixed cluster in
+// frame order, then the eigen system of the merged covariance
+static void kat_merge(int W, const double* clu, const double* fix, const double* poses, std::vector<IMUST>& xs,
+                      std::vector<PointCluster>& loc, PointCluster& f, PointCluster& add, V3& ev, M3& U) {
+  xs.resize(W);
   for (int i = 0; i < W; i++) {
     xs[i].R = m3_of(poses + 12 * i);
     xs[i].p = v3_of(poses + 12 * i + 9);
   }
-  std::vector<PointCluster> loc(W);
-  PointCluster f = clu_of(fix), add = f;
+  loc.resize(W);
+  f = clu_of(fix);
+  add = f;
   for (int i = 0; i < W; i++) {
     loc[i] = clu_of(clu + 13 * i);
     if (loc[i].N) {
@@ -58,9 +57,42 @@ void orc_kat_lidar_factor(int W, const double* clu, const double* fix, const dou
       add += t;
     }
   }
+  eig3(add.cov(), ev, U);
+}
+
+// The eigen system and merged cluster orc_kat_lidar_factor evaluates at:
+// eig (12: eigenvalues ascending, then the eigenvectors in columns, row-major)
+// and pcr (13: P 9, v 3, N).
+void orc_kat_lidar_eig(int W, const double* clu, const double* fix, const double* poses, double* eig, double* pcr) {
+  std::vector<IMUST> xs;
+  std::vector<PointCluster> loc;
+  PointCluster f, add;
   V3 ev;
   M3 U;
-  eig3(add.cov(), ev, U);
+  kat_merge(W, clu, fix, poses, xs, loc, f, add, ev, U);
+  for (int k = 0; k < 3; k++) eig[k] = ev[k];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) {
+      eig[3 + 3 * r + c] = U(r, c);
+      pcr[3 * r + c] = add.P(r, c);
+    }
+  for (int k = 0; k < 3; k++) pcr[9 + k] = add.v[k];
+  pcr[12] = (double)add.N;
+}
+
+// One LidarFactor voxel (factors.cpp:11-126): W local clusters (13 doubles
+// each: P 9, v 3, N), the fixed cluster, window poses (12 each: R 9, p 3).
+// The eigen system comes from the merged cluster at the given poses, as
+// tras_opt hands it over after a recut / residual pass. Outputs lambda_min,
+// JacT (6W) and the Hessian (6W x 6W, row-major). hess may be null.
+void orc_kat_lidar_factor(int W, const double* clu, const double* fix, const double* poses, double* res,
+                          double* jac, double* hess) {
+  std::vector<IMUST> xs;
+  std::vector<PointCluster> loc;
+  PointCluster f, add;
+  V3 ev;
+  M3 U;
+  kat_merge(W, clu, fix, poses, xs, loc, f, add, ev, U);
   LidarFactor lf(W);
   lf.push_voxel(loc, f, 1.0, ev, U, add);
   MatX H(6 * W, 6 * W);

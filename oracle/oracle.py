@@ -83,6 +83,7 @@ def lib():
         L.orc_capture_arm.argtypes = [P]
         L.orc_kat_p2p.argtypes = [dp] * 7
         L.orc_kat_lidar_factor.argtypes = [ctypes.c_int, dp, dp, dp, dp, dp, dp]
+        L.orc_kat_lidar_eig.argtypes = [ctypes.c_int, dp, dp, dp, dp, dp]
         L.orc_kat_imu.argtypes = [dp, ctypes.c_int, dp, dp, dp, dp, dp, ctypes.c_double, dp, dp]
         L.orc_kat_imu.restype = ctypes.c_double
         L.orc_capture_get.argtypes = [P, dp, ctypes.c_int]
@@ -201,6 +202,16 @@ def kat_lidar_factor(clusters, fix, poses, hess=True):
     h = np.zeros((6 * W, 6 * W))
     lib().orc_kat_lidar_factor(W, _d(clusters), _d(fix), _d(poses), _d(r), _d(j), _d(h) if hess else None)
     return r[0], j, h
+
+
+def kat_lidar_eig(clusters, fix, poses):
+    """The eigen system and merged cluster kat_lidar_factor evaluates at (evaluate_only_residual,
+    factors.cpp:137-150): (eig (12,) [eigenvalues ascending, eigenvectors in columns, row-major],
+    pcr (13,) [P9 v3 N])."""
+    clusters, fix, poses = _a(clusters), _a(fix), _a(poses)
+    e, c = np.zeros(12), np.zeros(13)
+    lib().orc_kat_lidar_eig(clusters.shape[0], _d(clusters), _d(fix), _d(poses), _d(e), _d(c))
+    return e, c
 
 
 def kat_imu(imu, bias0, dbias, x1, x2, noise, sg=1.0):

@@ -922,7 +922,9 @@ void launch_ba_control(vg_ctx* ctx, const CtlArg& ctl) { k_ba_control<<<1, 256, 
 // out (residual pass): the residual (evaluate_only_residual, which also stores
 // each factor's eigen system and merged cluster at these poses, as the
 // reference's does).
-int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_ring, double* out) {
+// G: the Hessian pass's chunk workgroups, nrb: the residual pass's workgroups
+// (ba_lidar_pass: the LM's own; vgx_ba_factors may choose others)
+static int lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_ring, int G, int nrb, double* out) {
   const int W = ctx->cfg.win_size;
   hipStream_t s = ctx->stream;
   BaDev d = carve(ctx);
@@ -942,7 +944,6 @@ int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_
   VG_HIP(hipMemcpyAsync(d.mpring, h + W * kX + 8, sizeof(ring), hipMemcpyHostToDevice, s));
   const int* nfp = ctx->map.counters + kCntFactors;
   if (hessian) {
-    const int G = std::min(kHessGridMax, ctx->ba.cap_f / hess_chunk(W) + 1);
     k_ba_hess<<<G, kHessThreads, hess_lds_bytes(W), s>>>(nfp, W, ctx->ba.fac_node, ctx->ba.fac_eig, ctx->ba.fac_pcr,
                                                         ctx->map.pcrs, d.mpring, d.xs, d.part, d.st, G, 0, d.imurec,
                                                         &ctx->st->imu_head, d.bias, d.imuout, nullptr);
@@ -953,7 +954,6 @@ int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_
     memcpy(out, h, nout * sizeof(double));
     return VG_OK;
   }
-  const int nrb = kResidBlocks;
   k_ba_resid<<<nrb, 256, 0, s>>>(nfp, W, ctx->ba.fac_node, ctx->map.pcr_fix, ctx->map.pcrs, d.mpring, d.xt,
                                  ctx->ba.fac_eig, ctx->ba.fac_pcr, d.rpart, d.st, nrb, 0, d.imurec, &ctx->st->imu_head,
                                  d.bias, d.imures, CtlArg{});
@@ -964,6 +964,71 @@ int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_
   for (int b = 0; b < nrb; b++) r += h[b];
   *out = r;
   return VG_OK;
+}
+
+int ba_lidar_pass(vg_ctx* ctx, bool hessian, const double* poses, const int* mp_ring, double* out) {
+  return lidar_pass(ctx, hessian, poses, mp_ring, ba_hess_grid(ctx), kResidBlocks, out);
+}
+
+// Test-only (vgx_ba_factors): both LiDAR factor passes on given factors,
+// through lidar_pass. nf factors, factor a the voxel of node fac_node[a]; the
+// nn nodes `nodes` carry their window clusters by physical slot (clus: nn x W x
+// 10 — P xx xy xz yy yz zz, v 3, N — written to map.pcrs[node * W + slot]) and
+// their fixed cluster (fix: nn x 10, to map.pcr_fix). The residual pass runs at
+// `poses` (W x kX) with ring mp_ring and leaves fac_eig / fac_pcr as tras_opt
+// hands them to the Hessian pass, which then runs at the same poses. G / nrb:
+// the passes' workgroup counts, 0 for the LM's own. Out: hl (packed lower
+// Hessian, gradient, residual), the residual pass's residual, fac_eig (nf x
+// 12) and fac_pcr (nf x 10). The context must not be stepped afterwards.
+int ba_factors_test(vg_ctx* ctx, int nf, const int* fac_node, int nn, const int* nodes, const double* clus,
+                    const double* fix, const double* poses, const int* mp_ring, int G, int nrb, double* hl,
+                    double* resid, double* eig, double* pcr) {
+  const int W = ctx->cfg.win_size;
+  if (sharded(ctx)) return VG_E_STATE;
+  if (nf < 0 || nf > ctx->ba.cap_f || nn < 0 || nn > ctx->map.cap_nodes) return VG_E_ARG;
+  if (G < 0 || G > kHessGridMax || nrb < 0 || nrb > kResidBlocks) return VG_E_ARG;
+  for (int i = 0; i < W; i++)
+    if (mp_ring[i] < 0 || mp_ring[i] >= W) return VG_E_ARG;
+  std::vector<char> given((size_t)ctx->map.cap_nodes, 0);
+  for (int k = 0; k < nn; k++) {
+    if (nodes[k] < 0 || nodes[k] >= ctx->map.cap_nodes) return VG_E_ARG;
+    given[nodes[k]] = 1;
+  }
+  for (int a = 0; a < nf; a++)  // a factor reads only clusters this call wrote
+    if (fac_node[a] < 0 || fac_node[a] >= ctx->map.cap_nodes || !given[fac_node[a]]) return VG_E_ARG;
+  hipStream_t s = ctx->stream;
+  auto clu_of = [](const double* c) {
+    Clu o;
+    for (int i = 0; i < 6; i++) o.P[i] = c[i];
+    for (int i = 0; i < 3; i++) o.v[i] = c[6 + i];
+    o.N = (int)c[9];
+    o.pad = 0;
+    return o;
+  };
+  std::vector<Clu> hc((size_t)nn * (W + 1));
+  for (int k = 0; k < nn; k++) {
+    Clu* row = &hc[(size_t)k * (W + 1)];
+    for (int j = 0; j < W; j++) row[j] = clu_of(&clus[((size_t)k * W + j) * 10]);
+    row[W] = clu_of(&fix[(size_t)k * 10]);
+    VG_HIP(hipMemcpyAsync(ctx->map.pcrs + (size_t)nodes[k] * W, row, (size_t)W * sizeof(Clu), hipMemcpyHostToDevice, s));
+    VG_HIP(hipMemcpyAsync(ctx->map.pcr_fix + nodes[k], row + W, sizeof(Clu), hipMemcpyHostToDevice, s));
+  }
+  if (nf > 0) VG_HIP(hipMemcpyAsync(ctx->ba.fac_node, fac_node, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
+  VG_HIP(hipMemcpyAsync(ctx->map.counters + kCntFactors, &nf, sizeof(int), hipMemcpyHostToDevice, s));
+  VG_HIP(hipStreamSynchronize(s));
+  VG_TRY(lidar_pass(ctx, false, poses, mp_ring, 0, nrb ? nrb : kResidBlocks, resid));
+  std::vector<Clu> fp((size_t)nf);
+  if (nf > 0) {
+    VG_HIP(hipMemcpyAsync(eig, ctx->ba.fac_eig, (size_t)nf * 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+    VG_HIP(hipMemcpyAsync(fp.data(), ctx->ba.fac_pcr, (size_t)nf * sizeof(Clu), hipMemcpyDeviceToHost, s));
+    VG_HIP(hipStreamSynchronize(s));
+  }
+  for (int a = 0; a < nf; a++) {
+    for (int i = 0; i < 6; i++) pcr[(size_t)a * 10 + i] = fp[a].P[i];
+    for (int i = 0; i < 3; i++) pcr[(size_t)a * 10 + 6 + i] = fp[a].v[i];
+    pcr[(size_t)a * 10 + 9] = (double)fp[a].N;
+  }
+  return lidar_pass(ctx, true, poses, mp_ring, G ? G : ba_hess_grid(ctx), 0, hl);
 }
 
 // Test-only (vgx_ba_control): one k_ba_control launch (the LM bookkeeping,

@@ -939,7 +939,7 @@ int state_blur_init(vg_ctx* ctx, const double* par, int npose, const float4* pts
 // window states / x_curr / IMU records (+ zero bias, ring head 0) -> DState; synchronous
 int state_load(vg_ctx* ctx, const double* xs, int nw, const double* xc, const double* recs, int nrec);
 // ba.hip (the driver), ba_factor.hip (ba_lidar_pass, ba_factor_normals,
-// ba_control_test), ba_solve.hip (ba_solve_test, ba_step_test)
+// ba_control_test, ba_factors_test), ba_solve.hip (ba_solve_test, ba_step_test)
 constexpr int kBaX = 24;       // per-frame state: R 9, p 3, v 3, bg 3, ba 3, g 3
 int ba_alloc(vg_ctx* ctx);
 // LM on the device state (window states, IMU_PRE records and bias records in
@@ -980,6 +980,9 @@ int ba_step_test(vg_ctx* ctx, const double* hl, const double* imuout, const doub
                  double* Hcalc, double* Jcalc);  // vgx_ba_step
 int ba_control_test(vg_ctx* ctx, double* sd, int* si, const double* imures, const double* rpart, int nrb, double* xs,
                     const double* xt, double* bias);  // vgx_ba_control
+int ba_factors_test(vg_ctx* ctx, int nf, const int* fac_node, int nn, const int* nodes, const double* clus,
+                    const double* fix, const double* poses, const int* mp_ring, int G, int nrb, double* hl,
+                    double* resid, double* eig, double* pcr);  // vgx_ba_factors
 // host_mirror.cpp: the host mirror's lifetime, absorption and accessors
 // (host_sync, host_stats_log below as well)
 void host_init(vg_ctx* ctx);

@@ -1256,6 +1256,30 @@ extern "C" int vgx_ba_control(vg_ctx* ctx, double* sd, int* si, const double* im
   return VG_OK;
 }
 
+// Test-only: the LM's two LiDAR factor passes on given factors (ba_factor.hip
+// ba_factors_test) — the residual pass (k_ba_resid), then the Hessian pass
+// (k_ba_hess without IMU factors, k_ba_hfinal) at the same poses, through the
+// body the host-driven LM's passes use. nf factors on the nodes fac_node[nf];
+// nn nodes `nodes` with their window clusters by physical slot (clus, nn x W x
+// 10: P xx xy xz yy yz zz, v 3, N) and fixed clusters (fix, nn x 10); poses
+// (W x 24); mp_ring[W]; G / nrb the passes' workgroup counts (0: the LM's own;
+// at most 256 / 512). Out: hl (packed lower 6W x 6W, 6W gradient, residual),
+// resid (the residual pass's sum), fac_eig (nf x 12: eigenvalues ascending,
+// eigenvectors row-major in columns) and fac_pcr (nf x 10). VG_E_ARG on a
+// factor count above the context's capacity, a node outside the map's, or a
+// factor on a node that `nodes` does not list; VG_E_STATE on a sharded
+// context. The context must not be stepped after.
+extern "C" int vgx_ba_factors(vg_ctx* ctx, int nf, const int* fac_node, int nn, const int* nodes, const double* clus,
+                              const double* fix, const double* poses, const int* mp_ring, int G, int nrb, double* hl,
+                              double* resid, double* fac_eig, double* fac_pcr) {
+  if (!ctx || (!fac_node && nf > 0) || ((!nodes || !clus || !fix) && nn > 0) || !poses || !mp_ring || !hl || !resid ||
+      ((!fac_eig || !fac_pcr) && nf > 0))
+    return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  return vg::ba_factors_test(ctx, nf, fac_node, nn, nodes, clus, fix, poses, mp_ring, G, nrb, hl, resid, fac_eig,
+                             fac_pcr);
+}
+
 // Test-only: one k_iekf_update launch on given sums (iekf.hip iekf_update_test:
 // nb >= 0 block partials through the ordered reduction, nb < 0 the 34 final
 // sums). G6_out holds 96 doubles (G6 15 x 6, then nnt). The context must not be

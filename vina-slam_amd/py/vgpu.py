@@ -688,6 +688,9 @@ def lib():
             L.vgx_ba_step.argtypes = [P, dp, dp, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, dp, dp, dp,
                                       dp, ip, dp, dp]
             L.vgx_ba_control.argtypes = [P, dp, ip, dp, dp, ctypes.c_int, dp, dp, dp, ip]
+        if hasattr(L, "vgx_ba_factors"):
+            L.vgx_ba_factors.argtypes = [P, ctypes.c_int, ip, ctypes.c_int, ip, dp, dp, dp, ip, ctypes.c_int,
+                                         ctypes.c_int, dp, dp, dp, dp]
         if hasattr(L, "vgx_memo_probe"):
             L.vgx_memo_probe.argtypes = [P, ip]
         if hasattr(L, "vgx_map_nodes"):
@@ -1654,6 +1657,32 @@ class Context:
         out = {k: float(sd[i]) for i, k in enumerate(self.BA_STATE_D)}
         out.update({k: int(si[i]) for i, k in enumerate(self.BA_STATE_I)})
         return out, xs, bias, acc.value
+
+    def ba_factors(self, W, fac_node, nodes, clus, fix, poses, mp_ring, G=0, nrb=0):
+        """The LM's LiDAR factor passes on given factors (vgx_ba_factors): the residual pass
+        (k_ba_resid), then the Hessian pass (k_ba_hess, k_ba_hfinal) at the same poses. fac_node
+        (nf,): each factor's node id; nodes (nn,) with clus (nn, W, 10) by physical slot [P xx xy xz
+        yy yz zz, v 3, N] and fix (nn, 10); poses (W, 24); mp_ring (W,): frame -> slot; G / nrb: the
+        passes' workgroup counts (0: the LM's own). Returns a dict: H (packed lower 6W x 6W), g (6W),
+        res (the Hessian pass's residual), resid (the residual pass's), eig (nf, 12), pcr (nf, 10).
+        The context must not be stepped afterwards."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        fac_node = np.ascontiguousarray(fac_node, dtype=np.int32).reshape(-1)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        clus = np.ascontiguousarray(clus, dtype=np.float64)
+        fix = np.ascontiguousarray(fix, dtype=np.float64)
+        poses = np.ascontiguousarray(poses, dtype=np.float64)
+        mp_ring = np.ascontiguousarray(mp_ring, dtype=np.int32)
+        nf, nn, L = fac_node.size, nodes.size, 6 * W
+        assert clus.size == nn * W * 10 and fix.size == nn * 10 and poses.size == W * 24 and mp_ring.size == W
+        nl = L * (L + 1) // 2
+        hl, resid = np.zeros(nl + L + 1), np.zeros(1)
+        eig, pcr = np.zeros((max(nf, 1), 12)), np.zeros((max(nf, 1), 10))
+        self._chk(lib().vgx_ba_factors(self.h, nf, fac_node.ctypes.data_as(ip), nn, nodes.ctypes.data_as(ip),
+                                       _d(clus), _d(fix), _d(poses), mp_ring.ctypes.data_as(ip), G, nrb, _d(hl),
+                                       _d(resid), _d(eig), _d(pcr)), "vgx_ba_factors")
+        return {"H": hl[:nl], "g": hl[nl: nl + L], "res": float(hl[nl + L]), "resid": float(resid[0]),
+                "eig": eig[:nf], "pcr": pcr[:nf]}
 
     LA_OPS = {"eig3": (0, 9, 12), "exp": (1, 3, 9), "exp_dt": (2, 4, 9), "log": (3, 9, 3), "jr": (4, 3, 9),
               "jr_inv": (5, 9, 9), "inverse6": (6, 36, 36), "inverse15": (7, 225, 225), "colpiv_qr": (8, 33, 3),
