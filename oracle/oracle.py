@@ -74,6 +74,8 @@ def lib():
         L.orc_step_deskew.argtypes = [P, fp, fp, fp, ctypes.c_int, ctypes.c_double, ctypes.c_double, dp, ctypes.c_int,
                                       dp]
         L.orc_deskew_only.argtypes = [P, fp, fp, ctypes.c_int, ctypes.c_double, ctypes.c_double, dp, ctypes.c_int]
+        L.orc_kat_prop.argtypes = [P, dp, dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
+        L.orc_kat_prop.restype = None
         L.orc_traj_len.argtypes = [P]
         L.orc_get_traj.argtypes = [P, dp]
         L.orc_path_len.argtypes = [P]
@@ -320,6 +322,16 @@ class Pipeline:
         imu = np.ascontiguousarray(imu, dtype=np.float64)
         npose = lib().orc_deskew_only(self.h, _f(out), _f(times), out.shape[0], beg, end, _d(imu), imu.shape[0])
         return out, npose
+
+    def kat_prop(self, state, imu, last_end, beg, end):
+        """propagate() alone (imu_ekf.cpp:28-94) from `state` (250) with last_pcl_end_time = last_end over
+        the samples imu (m, 7) -> the state after (250). The pipeline must not be stepped afterwards."""
+        s = np.ascontiguousarray(state, dtype=np.float64)
+        imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+        buf = imu if imu.size else np.zeros((1, 7))
+        out = np.zeros(250)
+        lib().orc_kat_prop(self.h, _d(s), _d(buf), imu.shape[0], last_end, beg, end, _d(out))
+        return out
 
     def shard(self, rank, world, allreduce):
         """Spatial-tile sharding: allreduce(np.ndarray) sums in place."""

@@ -991,6 +991,25 @@ int orc_deskew_only(void* h, float* xyz, const float* times, int n, double beg, 
   P->deskew(xyz, times, n);
   return (int)P->imu_poses.size();
 }
+// test hook: propagate() alone (IMUEKF::motion_blur's state / covariance part,
+// imu_ekf.cpp:28-94) from a given state (250: t, frame, cov) with
+// last_pcl_end_time = last_end, over m samples (t, gyr 3, acc 3); the noises
+// and the gravity scale are the pipeline's configuration. The pipeline must
+// not be stepped afterwards.
+void orc_kat_prop(void* h, const double* state, const double* imu, int m, double last_end, double beg, double end,
+                  double* out) {
+  Pipeline* P = (Pipeline*)h;
+  std::vector<ImuSample> imus(m);
+  for (int i = 0; i < m; i++) {
+    imus[i].t = imu[7 * i];
+    imus[i].gyr = v3(imu[7 * i + 1], imu[7 * i + 2], imu[7 * i + 3]);
+    imus[i].acc = v3(imu[7 * i + 4], imu[7 * i + 5], imu[7 * i + 6]);
+  }
+  state_from(P->x_curr, state);
+  P->last_pcl_end_time = last_end;
+  P->propagate(imus, beg, end);
+  state_to(P->x_curr, out);
+}
 void orc_get_stats(void* h, orc_stats* s) { *s = ((Pipeline*)h)->st; }
 void orc_release_far(void* h, long long* out) { ((Pipeline*)h)->release_far(out); }
 // test hook: every root voxel of surf_map (any order) — key x/y/z, its jour

@@ -107,6 +107,9 @@ int orc_step_deskew(void* h, const float* xyz, const float* inten, const float* 
                     const double* imu, int m, double* timing);
 /* propagation + deskew only, in place (returns the number of IMU poses) */
 int orc_deskew_only(void* h, float* xyz, const float* times, int n, double beg, double end, const double* imu, int m);
+/* test hook: the propagation alone from `state` (250) with last_pcl_end_time = last_end -> out (250) */
+void orc_kat_prop(void* h, const double* state, const double* imu, int m, double last_end, double beg, double end,
+                  double* out);
 /* Spatial-tile sharding of the restatement: this pipeline keeps
  * only the root voxels of tiles owned by `rank`; fn sums n doubles in place
  * over the ranks at every exchange point. Call before the first step. */

@@ -19,7 +19,9 @@ _CTR = mp.mpf(3.0 - 1e-6)
 
 
 def M(a):
-    """numpy fp64 array -> mpmath matrix (exact)."""
+    """numpy fp64 array -> mpmath matrix (exact); an mpmath matrix passes through."""
+    if isinstance(a, mp.matrix):
+        return a
     a = np.asarray(a, dtype=np.float64)
     if a.ndim == 1:
         a = a[:, None]
@@ -80,7 +82,7 @@ def Exp_dt(w, dt):
     n = norm(w)
     if n > _C1E7:
         K = hat(w / n)
-        a = n * mp.mpf(float(dt))
+        a = n * (dt if isinstance(dt, mp.mpf) else mp.mpf(float(dt)))
         return mp.eye(3) + mp.sin(a) * K + (1 - mp.cos(a)) * K * K
     return mp.eye(3)
 

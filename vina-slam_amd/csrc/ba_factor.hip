@@ -1086,6 +1086,66 @@ int ba_control_test(vg_ctx* ctx, double* sd, int* si, const double* imures, cons
   return VG_OK;
 }
 
+// Test-only (vgx_ba_imu): the IMU factor workgroups of the LM's three factor
+// passes on given records, through the launches the LM uses. The W-1 records
+// (kBaImuRec each) go to ring slots (head + k) % kMaxWin of DState::imurec —
+// every other slot holds `poison` — with imu_head = head; the bias records
+// ((W-1) x 12), xs and xt (W x kX) as given; the factor count is 0, so the
+// LiDAR workgroups have nothing to do. (a) k_ba_hess at xs, (b) k_ba_resid at
+// xt, (c) k_ba_resid_hess at xt; (b) and (c) with an empty CtlArg (err = null:
+// no bookkeeping runs; the LM state stays live, done = 0, because a finished
+// state makes both kernels return before their IMU lanes). imuout and imures
+// are filled with `poison` before each pass and returned whole (kMaxW x 931,
+// kMaxW): rows from W-1 on must still hold it. The context must not be stepped
+// afterwards.
+int ba_imu_test(vg_ctx* ctx, int head, const double* rec, const double* bias, const double* xs, const double* xt,
+                double poison, double* imuout_hess, double* imures_resid, double* imuout_rh, double* imures_rh) {
+  const int W = ctx->cfg.win_size, nimu = W - 1;
+  if (sharded(ctx)) return VG_E_STATE;
+  if (head < 0 || head >= kMaxWin || nimu < 1 || nimu > kMaxW) return VG_E_ARG;
+  hipStream_t s = ctx->stream;
+  BaDev d = carve(ctx);
+  DState* st = ctx->st;
+  std::vector<double> ring((size_t)kMaxWin * kImuRec, poison), po((size_t)kMaxW * 931, poison);
+  for (int k = 0; k < nimu; k++)
+    memcpy(&ring[(size_t)((head + k) % kMaxWin) * kImuRec], &rec[(size_t)k * kImuRec], kImuRec * sizeof(double));
+  BaState bs;
+  memset(&bs, 0, sizeof(bs));
+  bs.calc_hess = 1;
+  const int zero = 0, ringmp[kMaxW] = {0};
+  VG_HIP(hipMemcpy(st->imurec, ring.data(), ring.size() * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(&st->imu_head, &head, sizeof(int), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(d.bias, bias, (size_t)nimu * 12 * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(d.xs, xs, (size_t)W * kX * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(d.xt, xt, (size_t)W * kX * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(d.st, &bs, sizeof(bs), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(d.mpring, ringmp, sizeof(ringmp), hipMemcpyHostToDevice));
+  VG_HIP(hipMemcpy(ctx->map.counters + kCntFactors, &zero, sizeof(int), hipMemcpyHostToDevice));
+  auto arm = [&]() -> int {  // (the context's stream does not wait for the null stream)
+    VG_HIP(hipMemcpy(d.imuout, po.data(), (size_t)kMaxW * 931 * sizeof(double), hipMemcpyHostToDevice));
+    VG_HIP(hipMemcpy(d.imures, po.data(), (size_t)kMaxW * sizeof(double), hipMemcpyHostToDevice));
+    VG_HIP(hipDeviceSynchronize());
+    return VG_OK;
+  };
+  auto fetch = [&](double* out, double* res) -> int {
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(s));
+    if (out) VG_HIP(hipMemcpy(out, d.imuout, (size_t)kMaxW * 931 * sizeof(double), hipMemcpyDeviceToHost));
+    if (res) VG_HIP(hipMemcpy(res, d.imures, (size_t)kMaxW * sizeof(double), hipMemcpyDeviceToHost));
+    return VG_OK;
+  };
+  VG_TRY(arm());
+  launch_ba_hess(ctx, d);
+  VG_TRY(fetch(imuout_hess, nullptr));
+  VG_TRY(arm());
+  launch_ba_resid(ctx, d, CtlArg{});
+  VG_TRY(fetch(nullptr, imures_resid));
+  VG_TRY(arm());
+  launch_ba_resid_hess(ctx, d, CtlArg{});
+  VG_TRY(fetch(imuout_rh, imures_rh));
+  return VG_OK;
+}
+
 // the factors' eigenvectors (column 0 = the plane normal) and count, host copy
 int ba_factor_normals(vg_ctx* ctx, std::vector<double>& normals) {
   hipStream_t s = ctx->stream;  // stream-ordered: the context stream is non-blocking

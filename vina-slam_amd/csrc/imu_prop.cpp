@@ -110,4 +110,57 @@ void propagate(vg_ctx* ctx, HostPipe* P, const std::vector<Imu>& imus, double pc
   P->last_pcl_end_time = pcl_end;
 }
 
+// Test-only (vgx_scan_prop): k_scan_prop alone on a given x_curr block (x_in,
+// kXC: the frame state and the covariance) and n <= kPropMax samples, launched
+// through state_scan_begin without scan pointers or hand-off flags, with the
+// arguments stage_propagate gives it (prop_arg_fill: the noises and the gravity
+// scale are the context's). Out: DState::xc and xp after the launch, and the
+// block the host's propagate() makes of the same inputs on a scratch HostPipe.
+// More samples than the kernel's arrays hold never reach a launch.
+int scan_prop_test(vg_ctx* ctx, const double* x_in, int n, const double* imu, double last_end, double beg, double end,
+                   double* xc_out, double* xp_out, double* host_out) {
+  if (sharded(ctx)) {
+    ctx->err = "vgx_scan_prop: sharded context";
+    return VG_E_STATE;
+  }
+  if (n < 0 || n > kPropMax) {
+    ctx->err = "vgx_scan_prop: sample count outside [0, kPropMax]";
+    return VG_E_ARG;
+  }
+  const HostPipe* P = hp(ctx);
+  std::vector<PropArg> arg(1);
+  memset(&arg[0], 0, sizeof(PropArg));
+  prop_arg_fill(arg[0], ctx->cfg, P->sg, last_end, imu, n, beg, end);
+  DState* st = ctx->st;
+  VG_HIP(hipMemcpy(st->xc, x_in, kXC * sizeof(double), hipMemcpyHostToDevice));
+  VG_HIP(hipDeviceSynchronize());  // (the context's stream does not wait for the null stream)
+  VG_TRY(state_scan_begin(ctx, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &arg[0]));
+  VG_HIP(hipStreamSynchronize(ctx->stream));
+  VG_HIP(hipMemcpy(xc_out, st->xc, kXC * sizeof(double), hipMemcpyDeviceToHost));
+  VG_HIP(hipMemcpy(xp_out, st->xp, kXC * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<HostPipe> S(1);
+  hx_get_block(S[0].x_curr, x_in);
+  S[0].last_pcl_end_time = last_end;
+  S[0].sg = P->sg;
+  propagate(ctx, &S[0], to_imus(imu, n), beg, end);
+  hx_put_block(S[0].x_curr, host_out);
+  return VG_OK;
+}
+
+// Test-only (vgx_imu_record): HImuPre::push_imu + record() on given biases,
+// samples (n x 7), gravity scale and 6 x 6 noises. Host code only.
+int imu_record_test(const double* bg, const double* ba, const double* imu, int n, double sg, const double* noise_meas,
+                    const double* noise_walk, double* rec) {
+  M6 nm, nw;
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) {
+      nm(r, c) = noise_meas[r * 6 + c];
+      nw(r, c) = noise_walk[r * 6 + c];
+    }
+  HImuPre q(v3(bg[0], bg[1], bg[2]), v3(ba[0], ba[1], ba[2]));
+  q.push_imu(to_imus(imu, n), nm, nw, sg);
+  q.record(rec);
+  return VG_OK;
+}
+
 }  // namespace vg

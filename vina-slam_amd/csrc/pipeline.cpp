@@ -194,18 +194,7 @@ int stage_propagate(vg_ctx* ctx, const double* imu, int m, double beg, double en
   // only the device has that scan's state, so it propagates there
   P->begin_prop = ctx->mapping && prop_on_device(ctx, P, m, dev);  // (a frozen scan: on the host, frozen_step)
   if (P->begin_prop) {
-    PropArg& a = P->prop;
-    const vg_config& c = ctx->cfg;
-    a.n = m;
-    a.last_end = P->last_pcl_end_time;
-    a.beg = beg;
-    a.end = end;
-    a.sg = P->sg;
-    a.cov_gyr = c.odo_cov_gyr;
-    a.cov_acc = c.odo_cov_acc;
-    a.rdw_gyr = c.odo_rdw_gyr;
-    a.rdw_acc = c.odo_rdw_acc;
-    if (m > 0) memcpy(a.imu, imu, (size_t)m * 7 * sizeof(double));
+    prop_arg_fill(P->prop, ctx->cfg, P->sg, P->last_pcl_end_time, imu, m, beg, end);
     P->poses.clear();
     P->x_curr.t = end;
     P->last_pcl_end_time = end;

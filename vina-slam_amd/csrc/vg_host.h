@@ -260,6 +260,21 @@ static inline std::vector<Imu> to_imus(const double* imu, int m) {
   return imus;
 }
 
+// k_scan_prop's arguments for a scan with m <= kPropMax samples (stage_propagate; vgx_scan_prop)
+static inline void prop_arg_fill(PropArg& a, const vg_config& c, double sg, double last_end, const double* imu, int m,
+                                 double beg, double end) {
+  a.n = m;
+  a.last_end = last_end;
+  a.beg = beg;
+  a.end = end;
+  a.sg = sg;
+  a.cov_gyr = c.odo_cov_gyr;
+  a.cov_acc = c.odo_cov_acc;
+  a.rdw_gyr = c.odo_rdw_gyr;
+  a.rdw_acc = c.odo_rdw_acc;
+  if (m > 0) memcpy(a.imu, imu, (size_t)m * 7 * sizeof(double));
+}
+
 // pipeline.cpp
 int flush_deferred(vg_ctx* ctx, HostPipe* P);  // the deferred scan opening and window push, on their own
 // imu_prop.cpp

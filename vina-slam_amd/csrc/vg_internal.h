@@ -983,6 +983,9 @@ int ba_control_test(vg_ctx* ctx, double* sd, int* si, const double* imures, cons
 int ba_factors_test(vg_ctx* ctx, int nf, const int* fac_node, int nn, const int* nodes, const double* clus,
                     const double* fix, const double* poses, const int* mp_ring, int G, int nrb, double* hl,
                     double* resid, double* eig, double* pcr);  // vgx_ba_factors
+int ba_imu_test(vg_ctx* ctx, int head, const double* rec, const double* bias, const double* xs, const double* xt,
+                double poison, double* imuout_hess, double* imures_resid, double* imuout_rh,
+                double* imures_rh);  // vgx_ba_imu
 // host_mirror.cpp: the host mirror's lifetime, absorption and accessors
 // (host_sync, host_stats_log below as well)
 void host_init(vg_ctx* ctx);
@@ -1003,6 +1006,11 @@ int host_memo_probe(vg_ctx* ctx, int* out);  // map_memo_probe with the context'
 int iekf_update_test(vg_ctx* ctx, int nb, const double* partials, int n_points, const double* x_curr,
                      const double* x_prop, int it, int rematch, double* x_out, double* G6_out,
                      int* flags_out);  // vgx_iekf_update
+// imu_prop.cpp
+int scan_prop_test(vg_ctx* ctx, const double* x_in, int n, const double* imu, double last_end, double beg, double end,
+                   double* xc_out, double* xp_out, double* host_out);  // vgx_scan_prop
+int imu_record_test(const double* bg, const double* ba, const double* imu, int n, double sg, const double* noise_meas,
+                    const double* noise_walk, double* rec);  // vgx_imu_record
 // shard.cpp
 int shard_alloc(vg_ctx* ctx);
 void shard_free(vg_ctx* ctx);

@@ -1292,6 +1292,42 @@ extern "C" int vgx_iekf_update(vg_ctx* ctx, int nb, const double* partials, int 
   return vg::iekf_update_test(ctx, nb, partials, n_points, x_curr, x_prop, it, rematch, x_out, G6_out, flags_out);
 }
 
+// Test-only: k_scan_prop alone (imu_prop.cpp scan_prop_test) on the x_curr block
+// x_in (kXC doubles: frame state, 15 x 15 covariance) and n samples of (t, gyr,
+// acc); the noises and the gravity scale are the context's. Out: DState::xc and
+// xp after the launch and the host propagate()'s block from the same inputs
+// (kXC each). VG_E_ARG on n < 0 or n > kPropMax (48), before any launch;
+// VG_E_STATE on a sharded context. The context must not be stepped after.
+extern "C" int vgx_scan_prop(vg_ctx* ctx, const double* x_in, int n, const double* imu, double last_end, double beg,
+                             double end, double* xc_out, double* xp_out, double* host_out) {
+  if (!ctx || !x_in || (!imu && n > 0) || !xc_out || !xp_out || !host_out) return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  return vg::scan_prop_test(ctx, x_in, n, imu, last_end, beg, end, xc_out, xp_out, host_out);
+}
+
+// Test-only: the IMU factor workgroups of k_ba_hess (at xs), k_ba_resid (at xt)
+// and k_ba_resid_hess (at xt) on W-1 given records in ring slots (head + k) %
+// kMaxWin (ba_factor.hip ba_imu_test). Out: imuout of the first and the third
+// (16 x 931 each), imures of the second and the third (16 each), rows past W-1
+// still `poison`. VG_E_ARG on a head outside the ring, VG_E_STATE on a sharded
+// context. The context must not be stepped after.
+extern "C" int vgx_ba_imu(vg_ctx* ctx, int head, const double* rec, const double* bias, const double* xs,
+                          const double* xt, double poison, double* imuout_hess, double* imures_resid,
+                          double* imuout_rh, double* imures_rh) {
+  if (!ctx || !rec || !bias || !xs || !xt || !imuout_hess || !imures_resid || !imuout_rh || !imures_rh) return VG_E_ARG;
+  VG_TRY(vg::host_sync(ctx));
+  return vg::ba_imu_test(ctx, head, rec, bias, xs, xt, poison, imuout_hess, imures_resid, imuout_rh, imures_rh);
+}
+
+// Test-only, host only (no context, no HIP call): HImuPre::push_imu + record()
+// on biases bg, ba, n samples of (t, gyr, acc), the gravity scale and the 6 x 6
+// noises (row-major) -> the kBaImuRec (289) doubles of the record.
+extern "C" int vgx_imu_record(const double* bg, const double* ba, const double* imu, int n, double sg,
+                              const double* noise_meas, const double* noise_walk, double* rec) {
+  if (!bg || !ba || (!imu && n > 0) || n < 0 || !noise_meas || !noise_walk || !rec) return VG_E_ARG;
+  return vg::imu_record_test(bg, ba, imu, n, sg, noise_meas, noise_walk, rec);
+}
+
 int vg_lio_kdtree(vg_ctx* ctx, const float* xyz, int n, double* state, int* valid, int* iters) {
   if (!ctx || (!xyz && n > 0) || n < 0 || !state || !valid || !iters) return VG_E_ARG;
   return host_lio_kdtree(ctx, xyz, n, state, valid, iters);

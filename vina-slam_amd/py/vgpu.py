@@ -20,6 +20,11 @@ REPO = os.path.dirname(PKG)
 LIB = os.environ.get("VINA_GPU_LIB") or os.path.join(PKG, "lib", "libvina_gpu.so")
 HEADER = os.path.join(REPO, "include", "vina_gpu.h")
 STATE_LEN = 250
+XC_LEN = 249       # a frame state (24) and its 15 x 15 covariance (DState::xc)
+PROP_MAX = 48      # kPropMax: IMU samples k_scan_prop's arguments hold
+MAX_WIN = 32       # kMaxWin: slots of the IMU record ring
+IMU_REC = 289      # kBaImuRec
+BA_MAX_W = 16      # kMaxW: rows of imuout / imures
 
 
 class Capacity(ctypes.Structure):
@@ -703,6 +708,11 @@ def lib():
         if hasattr(L, "vgx_iekf_update"):
             L.vgx_iekf_update.argtypes = [P, ctypes.c_int, dp, ctypes.c_int, dp, dp, ctypes.c_int, ctypes.c_int, dp,
                                           dp, ip]
+        if hasattr(L, "vgx_scan_prop"):
+            L.vgx_scan_prop.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        dp, dp, dp]
+            L.vgx_ba_imu.argtypes = [P, ctypes.c_int, dp, dp, dp, dp, ctypes.c_double, dp, dp, dp, dp]
+            L.vgx_imu_record.argtypes = [dp, dp, dp, ctypes.c_int, ctypes.c_double, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -1712,6 +1722,54 @@ class Context:
         self._chk(lib().vgx_iekf_update(self.h, nb, _d(p), n_points, _d(xc), _d(xp), it, rematch, _d(xo), _d(g),
                                         fl.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "vgx_iekf_update")
         return xo, g[:90].reshape(15, 6), g[90:], fl
+
+    def scan_prop(self, x_in, imu, last_end, beg, end):
+        """k_scan_prop alone (vgx_scan_prop) on the x_curr block x_in (249: frame state 24, cov 225)
+        and the samples imu (n, 7: t, gyr, acc), n <= PROP_MAX (more: VgError -1 before any launch);
+        the noises and the gravity scale are the context's. Returns (xc, xp, host): DState::xc and
+        xp after the launch and the host propagate()'s block of the same inputs. The context must
+        not be stepped afterwards."""
+        x_in = np.ascontiguousarray(x_in, dtype=np.float64)
+        imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+        assert x_in.size == XC_LEN
+        xc, xp, host = np.zeros(XC_LEN), np.zeros(XC_LEN), np.zeros(XC_LEN)
+        buf = imu if imu.size else np.zeros((1, 7))
+        self._chk(lib().vgx_scan_prop(self.h, _d(x_in), imu.shape[0], _d(buf), last_end, beg, end, _d(xc), _d(xp),
+                                      _d(host)), "vgx_scan_prop")
+        return xc, xp, host
+
+    def ba_imu(self, W, head, rec, bias, xs, xt, poison=np.nan):
+        """The IMU factor workgroups of the LM's factor passes on given records (vgx_ba_imu): rec
+        (W-1, 289) in ring slots (head + k) % MAX_WIN, bias (W-1, 12), xs and xt (W, 24); W is the
+        context's win_size. Returns a dict of whole buffers, rows past W-1 still `poison`: hess
+        (16, 931: k_ba_hess at xs), resid (16: k_ba_resid at xt), rh_out and rh_res (k_ba_resid_hess
+        at xt). The context must not be stepped afterwards."""
+        rec = np.ascontiguousarray(rec, dtype=np.float64)
+        bias = np.ascontiguousarray(bias, dtype=np.float64)
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        xt = np.ascontiguousarray(xt, dtype=np.float64)
+        assert rec.size == (W - 1) * IMU_REC and bias.size == (W - 1) * 12 and xs.size == W * 24 and xt.size == W * 24
+        o = {"hess": np.zeros((BA_MAX_W, 931)), "resid": np.zeros(BA_MAX_W), "rh_out": np.zeros((BA_MAX_W, 931)),
+             "rh_res": np.zeros(BA_MAX_W)}
+        self._chk(lib().vgx_ba_imu(self.h, head, _d(rec), _d(bias), _d(xs), _d(xt), poison, _d(o["hess"]),
+                                   _d(o["resid"]), _d(o["rh_out"]), _d(o["rh_res"])), "vgx_ba_imu")
+        return o
+
+
+def imu_record(bg, ba, imu, sg, noise_meas, noise_walk):
+    """HImuPre::push_imu + record() on the host (vgx_imu_record; no context, no device): biases,
+    samples (n, 7), the gravity scale and the 6 x 6 noises -> the 289-double record."""
+    bg = np.ascontiguousarray(bg, dtype=np.float64)
+    ba = np.ascontiguousarray(ba, dtype=np.float64)
+    imu = np.ascontiguousarray(imu, dtype=np.float64).reshape(-1, 7)
+    nm = np.ascontiguousarray(noise_meas, dtype=np.float64)
+    nw = np.ascontiguousarray(noise_walk, dtype=np.float64)
+    assert bg.size == 3 and ba.size == 3 and nm.size == 36 and nw.size == 36
+    rec = np.zeros(IMU_REC)
+    r = lib().vgx_imu_record(_d(bg), _d(ba), _d(imu), imu.shape[0], sg, _d(nm), _d(nw), _d(rec))
+    if r != 0:
+        raise VgError("vgx_imu_record failed (%d)" % r)
+    return rec
 
 
 class Sync:
