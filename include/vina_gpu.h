@@ -873,6 +873,94 @@ _Static_assert(sizeof(vg_frontier_params) == 56 && sizeof(vg_frontier_rec) == 64
 int vg_frontiers(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm,
                  int32_t* labels, vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
 
+/* ---- View gain: the unknown space a 2-D sensor would see from candidate cells -----
+ * What a robot would learn by driving to a cell: from cell (ox, oy) of an nx x ny
+ * grid of VG_OCC_* values (i = iy nx + ix as in vg_occupancy), which cells does a
+ * 2-D sensor of range R cells see, and how many of them are unknown? All
+ * arithmetic is integer, so every output byte is a pure function of the inputs. A
+ * byte value that is neither VG_OCC_OCCUPIED nor VG_OCC_UNKNOWN is free, as in
+ * vg_clearance.
+ *
+ * Targets: 8R per viewpoint, every offset (dx, dy) with max(|dx|, |dy|) = R. For a
+ * target let n = R, ax = |dx|, ay = |dy| and sx, sy the signs of dx, dy.
+ * Ray cells: cell k of the ray, k = 1 .. n, is
+ *   c_k = (ox + sx ((2 k ax + n) div (2 n)), oy + sy ((2 k ay + n) div (2 n))),
+ * div the division of non-negative integers: rounding half away from zero, so the
+ * set is symmetric under the grid's eight reflections, and consecutive cells
+ * differ by at most 1 in each coordinate. (The remainder may be kept
+ * incrementally; that is exact.)
+ * The walk: c_0 is the origin. A ray walks k = 1, 2, ... with u = 0 and at each k
+ * tests in this order:
+ *   1. c_k outside the grid: the ray ends (open).
+ *   2. (cx - ox)^2 + (cy - oy)^2 > R^2: the ray ends (open).
+ *   3. the step from c_{k-1} to c_k is diagonal and both cells it squeezes
+ *      between, (c_{k-1}.x, c_k.y) and (c_k.x, c_{k-1}.y), are VG_OCC_OCCUPIED: the
+ *      ray ends (blocked). (Both lie inside the grid.) This is vg_navfn's
+ *      no-corner-cutting rule: a one-cell-thick diagonal wall does not leak.
+ *   4. c_k becomes visible.
+ *   5. grid[c_k] == VG_OCC_OCCUPIED: the ray ends (blocked).
+ *   6. grid[c_k] == VG_OCC_UNKNOWN: u += 1; with max_unknown > 0 and u >=
+ *      max_unknown the ray ends (open).
+ *   7. after k = n the ray ends (open).
+ * The visible set of a viewpoint is the union over its 8R rays, plus the origin's
+ * own cell. Each cell counts once, however many rays cross it.
+ * Status: an origin outside the grid gives VG_VIEW_OUTSIDE, one on an occupied
+ * cell VG_VIEW_BLOCKED; both give zero counts and contribute to nothing. Anything
+ * else is VG_VIEW_OK. */
+#define VG_VIEW_MAX_RADIUS 255
+#define VG_VIEW_OK       0
+#define VG_VIEW_OUTSIDE  1   /* the origin is outside the grid */
+#define VG_VIEW_BLOCKED  2   /* the origin is an occupied cell */
+typedef struct vg_view_params {    /* 56 bytes, no implicit padding */
+  int    nx, ny;        /* as vg_frontier_params; nx ny <= VG_OCC_MAX_CELLS, each <= VG_CLR_MAX_SIDE */
+  int    radius;        /* R, cells: 1 .. VG_VIEW_MAX_RADIUS */
+  int    max_unknown;   /* >= 0; > 0: a ray ends at its max_unknown-th unknown cell */
+  int    flags;         /* must be 0 */
+  int    pad;
+  double reserved[4];
+} vg_view_params;
+typedef struct vg_view_rec {       /* 32 bytes, no implicit padding */
+  int32_t ix, iy, status;          /* the viewpoint as given; VG_VIEW_* */
+  int32_t n_visible;               /* cells of the visible set */
+  int32_t n_unknown, n_free, n_occupied;  /* ... by class; they sum to n_visible */
+  int32_t n_rays_open;             /* rays of the 8R that ended open */
+} vg_view_rec;
+typedef struct vg_view_summary {   /* 128 bytes, no implicit padding; every field is reproducible */
+  int64_t n_views, n_ok, n_outside, n_blocked;  /* viewpoints; by status */
+  int64_t rays;                    /* 8R per VG_VIEW_OK viewpoint */
+  int64_t max_unknown_seen;        /* the largest n_unknown of an OK viewpoint; 0 without one */
+  int64_t best_view;               /* the index of the viewpoint that has it, among equals the smallest index;
+                                      -1 without an OK viewpoint */
+  int64_t cells_seen, unknown_seen;  /* cells in at least one viewpoint's visible set; the unknown ones among
+                                        them: the gain of the whole set, not the sum of the per-view gains */
+  int64_t reserved[7];
+} vg_view_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vg_view_params) == 56 && sizeof(vg_view_rec) == 32 && sizeof(vg_view_summary) == 128,
+              "the view records have no implicit padding");
+#else
+_Static_assert(sizeof(vg_view_params) == 56 && sizeof(vg_view_rec) == 32 && sizeof(vg_view_summary) == 128,
+               "the view records have no implicit padding");
+#endif
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call on
+ * this context left on the device (VG_E_STATE when there was no such call or its nx,
+ * ny differ from prm's). views: n_views pairs (ix, iy), 1 <= n_views <=
+ * VG_NAV_MAX_POINTS; recs: one record per viewpoint, in the order given. A cell
+ * named twice gets two records and counts twice in seen. seen: nx ny int32, or
+ * NULL: not copied out; seen[i] is the number of VG_VIEW_OK viewpoints whose
+ * visible set holds cell i. The counts are integer atomics: seen and the summary do
+ * not depend on the order of the viewpoints, and the seen planes of two calls over
+ * a split of the viewpoints add up to the plane of one call. All planes are device
+ * buffers allocated on first use and re-used; only the records, seen (when asked
+ * for) and the summary leave the device. NULL ctx, prm, views, recs or out; nx or
+ * ny < 1 or > VG_CLR_MAX_SIDE, or nx ny > VG_OCC_MAX_CELLS; radius < 1 or >
+ * VG_VIEW_MAX_RADIUS; max_unknown < 0; flags != 0; n_views < 1 or >
+ * VG_NAV_MAX_POINTS: VG_E_ARG, and nothing is written. Legal where vg_clearance is:
+ * completes outstanding work first; unsharded contexts only (VG_E_STATE with world
+ * > 1). */
+int vg_view_gain(vg_ctx* ctx, const int8_t* grid, const vg_view_params* prm, const int32_t* views, int n_views,
+                 vg_view_rec* recs, int32_t* seen, vg_view_summary* out);
+
 /* ---- Change layer: scan-vs-map evidence summed over many scans ----------------
  * One scan's classes do not say what changed: leaf planes reach to their cube's
  * faces past a real edge, so a static scene already shows some VANISHED. The

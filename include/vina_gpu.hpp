@@ -265,6 +265,45 @@ class LioCore {
     r.recs.resize((size_t)r.summary.n_written);
     return r;
   }
+  // the view gain (vina_gpu.h "View gain") from the cells views (ix, iy pairs) of grid (nx ny cells of VG_OCC_*;
+  // null: the grid the last occupancy() call left on the device): one record per viewpoint in the order given
+  struct ViewGain {
+    std::vector<vg_view_rec> recs;
+    std::vector<int32_t> seen;  // filled only where asked for
+    vg_view_summary summary;
+    // the indices of the recs worth visiting, best first: those with VG_VIEW_OK and n_unknown >= min_gain. With
+    // pots (one per record, e.g. the frontier records' best_pot) a comes before b when n_unknown_a (pot_b + 1) >
+    // n_unknown_b (pot_a + 1), exact in 64 bits (the products stay below 2^50); ties go to the smaller pot, then
+    // the smaller index. Without pots (empty): by descending n_unknown, then index
+    std::vector<int> order(const std::vector<uint32_t>& pots = {}, int min_gain = 1) const {
+      std::vector<int> o;
+      for (size_t k = 0; k < recs.size(); k++)
+        if (recs[k].status == VG_VIEW_OK && recs[k].n_unknown >= min_gain) o.push_back((int)k);
+      const bool use = pots.size() == recs.size() && !pots.empty();
+      std::sort(o.begin(), o.end(), [&](int a, int b) {
+        const int64_t ga = recs[a].n_unknown, gb = recs[b].n_unknown;
+        if (!use) return ga != gb ? ga > gb : a < b;
+        const int64_t lhs = ga * ((int64_t)pots[b] + 1), rhs = gb * ((int64_t)pots[a] + 1);
+        if (lhs != rhs) return lhs > rhs;
+        return pots[a] != pots[b] ? pots[a] < pots[b] : a < b;
+      });
+      return o;
+    }
+  };
+  ViewGain view_gain(const int8_t* grid, const vg_view_params& prm, const std::vector<int32_t>& views,
+                     bool want_seen = false) {
+    ViewGain r;
+    size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    if (cells > (size_t)VG_OCC_MAX_CELLS) cells = 1;
+    if (want_seen) r.seen.resize(cells);
+    const size_t n = views.size() / 2;
+    r.recs.resize(n ? n : 1);
+    check(vg_view_gain(ctx_, grid, &prm, views.data(), (int)n, r.recs.data(), want_seen ? r.seen.data() : nullptr,
+                       &r.summary),
+          "vg_view_gain");
+    r.recs.resize(n);
+    return r;
+  }
   // the change layer (vina_gpu.h "Change layer"): begin / end on the map's owner; accumulate on the
   // owner or any tracker attached to it; prm / q null: the defaults
   void change_begin(const vg_change_params* prm = nullptr) { check(vg_change_begin(ctx_, prm), "vg_change_begin"); }

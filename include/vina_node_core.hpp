@@ -170,6 +170,18 @@ struct ExploreGoal {
   LioCore::Frontiers frontiers;  // every kept frontier and the summary (labels only where asked for)
 };
 
+// The same, chosen by view gain (NodeCore::explore_goal_gain)
+struct ExploreGoalGain {
+  bool found = false;            // a reachable frontier from whose best_cell at least min_gain unknown cells show
+  vg_frontier_rec frontier = {}; // the chosen one: frontiers.recs[order[0]]
+  vg_view_rec view = {};         // what its best_cell sees: gain.recs[order[0]]
+  double goal_xy[2] = {0, 0};    // that cell's centre, metres
+  Plan path;                     // from the goal's cell down to the robot's, as ExploreGoal::path
+  LioCore::Frontiers frontiers;  // every kept frontier
+  LioCore::ViewGain gain;        // record k: the view from frontiers.recs[k].best_cell
+  std::vector<int> order;        // LioCore::ViewGain::order() over the frontiers' best_pot
+};
+
 class NodeCore {
  public:
   // cfg.cold_start = 1 for a run from a bag (the node's initialization,
@@ -548,6 +560,71 @@ class NodeCore {
     if (e.frontiers.recs.empty()) return e;
     e.found = true;
     e.frontier = e.frontiers.recs[(size_t)e.frontiers.order()[0]];
+    cell_xy(e.frontier.best_cell, e.goal_xy);
+    const LioCore::NavPaths r = lio_.nav_paths({e.frontier.best_cell % cm_nx_, e.frontier.best_cell / cm_nx_}, max_len);
+    e.path.status = r.status[0], e.path.cost = r.cost[0];
+    e.path.cells.assign(r.cells.begin(), r.cells.begin() + r.len[0]);
+    for (const int32_t c : e.path.cells) {
+      double xy[2];
+      cell_xy(c, xy);
+      e.path.xy.push_back(xy[0]), e.path.xy.push_back(xy[1]);
+    }
+    return e;
+  }
+
+  // The view gain (vg_view_gain) at every frontier's best_cell, on the grid of the last occupancy_grid() where it
+  // lies on the device (no vg_occupancy may have run on the context since): what a 2-D sensor of range radius_m
+  // (rounded to whole cells of the last costmap(), 1 .. VG_VIEW_MAX_RADIUS) would see from where the robot would
+  // stop. fs: frontiers(true, ...)'s, so that every record has its best_cell; record k belongs to fs.recs[k].
+  // Completes outstanding work.
+  LioCore::ViewGain frontier_gain(const LioCore::Frontiers& fs, double radius_m, int max_unknown = 0,
+                                  bool want_seen = false) {
+    finish();
+    if (!cm_nx_) throw Error(VG_E_STATE, "frontier_gain: no costmap() on this node yet");
+    vg_view_params q = {};
+    const double cells = std::floor(radius_m / cm_res_ + 0.5);
+    q.nx = cm_nx_, q.ny = cm_ny_, q.max_unknown = max_unknown;
+    q.radius = !(cells >= 1.0) ? 1 : cells > (double)VG_VIEW_MAX_RADIUS ? VG_VIEW_MAX_RADIUS : (int)cells;
+    std::vector<int32_t> views;
+    for (const vg_frontier_rec& r : fs.recs) {
+      if (r.best_cell < 0) throw Error(VG_E_ARG, "frontier_gain: a frontier without best_cell (frontiers(true) gives it)");
+      views.push_back(r.best_cell % cm_nx_), views.push_back(r.best_cell / cm_nx_);
+    }
+    return lio_.view_gain(nullptr, q, views, want_seen);
+  }
+  // the frontier records' best_pot, as ViewGain::order() takes them
+  static std::vector<uint32_t> frontier_pots(const LioCore::Frontiers& fs) {
+    std::vector<uint32_t> p;
+    for (const vg_frontier_rec& r : fs.recs) p.push_back(r.best_pot);
+    return p;
+  }
+
+  // explore_goal() with the goal chosen by what the robot would learn there: its chain up to the frontiers, then
+  // frontier_gain() at every kept frontier's best_cell, and the goal is the first in ViewGain::order(best_pot,
+  // min_gain): the most unknown cells in view per cost to drive there. found is false where no reachable frontier
+  // shows at least min_gain unknown cells. The path comes from vg_nav_paths as in explore_goal().
+  ExploreGoalGain explore_goal_gain(const double robot_xy[2], const OccupancyGridParams& P, double inscribed,
+                                    double inflation, double scaling, double radius_m, int min_gain = 1,
+                                    int max_unknown = 0, int min_size = 0, const vg_nav_params* prm = nullptr,
+                                    int max_len = 65536) {
+    const OccupancyGrid g = occupancy_grid(P);
+    costmap(g, inscribed, inflation, scaling, 0, true);
+    vg_nav_params q = {};
+    if (prm) q = *prm;
+    q.nx = cm_nx_, q.ny = cm_ny_;
+    const double fx = std::floor((robot_xy[0] - cm_x0_) / cm_res_), fy = std::floor((robot_xy[1] - cm_y0_) / cm_res_);
+    const std::vector<int32_t> robot = {fx >= 0.0 && fx < (double)cm_nx_ ? (int32_t)fx : (int32_t)-1,
+                                        fy >= 0.0 && fy < (double)cm_ny_ ? (int32_t)fy : (int32_t)-1};
+    ExploreGoalGain e;
+    e.path.summary = lio_.navfn(nullptr, q, robot, false).summary;
+    e.frontiers = frontiers(true, min_size);
+    if (e.frontiers.recs.empty()) return e;
+    e.gain = frontier_gain(e.frontiers, radius_m, max_unknown);
+    e.order = e.gain.order(frontier_pots(e.frontiers), min_gain);
+    if (e.order.empty()) return e;
+    e.found = true;
+    e.frontier = e.frontiers.recs[(size_t)e.order[0]];
+    e.view = e.gain.recs[(size_t)e.order[0]];
     cell_xy(e.frontier.best_cell, e.goal_xy);
     const LioCore::NavPaths r = lio_.nav_paths({e.frontier.best_cell % cm_nx_, e.frontier.best_cell / cm_nx_}, max_len);
     e.path.status = r.status[0], e.path.cost = r.cost[0];

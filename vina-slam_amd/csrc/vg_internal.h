@@ -474,6 +474,17 @@ struct FrontierBufs {
   int combine = 1;            // k_fr_stats: lanes of a wave on one component add once (vgx_frontier_combine)
   KernelTimer t;              // around the call's kernels; ms: the last call's (vgx_frontier_ms)
 };
+// vg_view_gain planes and staging (view.hip), allocated on first use and grown
+struct ViewBufs {
+  DevBuf<int8_t> grid;        // cells: a host grid's upload (grid == NULL reads OccBufs::grid instead)
+  DevBuf<int> views;          // 2 VG_NAV_MAX_POINTS: the viewpoints
+  DevBuf<vg_view_rec> rec;    // one per viewpoint, grown to the count a call brings
+  DevBuf<int> seen;           // cells: the viewpoints per cell (kept whether or not the caller asks for it: the
+                              // summary's cells_seen and unknown_seen are counted from it)
+  DevBuf<unsigned long long> sum;  // vg_view_summary's 16 slots, then the packed key behind best_view
+  int stage = 0;              // k_view_rays: the window's classes staged in LDS where they fit (vgx_view_stage)
+  KernelTimer t;              // around the call's kernels; ms: the last call's (vgx_view_ms)
+};
 // The change layer (vina_gpu.h "Change layer"; change.hip, change_host.cpp): a
 // side structure of the context that owns a frozen map, never part of DevMap.
 // Only integer atomics write it, one accumulate call at a time (vg_ctx::change_mu of the owner).
@@ -662,6 +673,7 @@ struct vg_ctx {
   vg::ClrBufs clr;           // vg_clearance staging and planes (clearance.hip), allocated on first use
   vg::NavBufs nav;           // vg_navfn / vg_nav_paths planes (navfn.hip), allocated on first use
   vg::FrontierBufs fr;       // vg_frontiers planes (frontier.hip), allocated on first use
+  vg::ViewBufs view;         // vg_view_gain planes (view.hip), allocated on first use
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
@@ -1126,6 +1138,11 @@ int nav_paths_dev(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len,
 // by the caller
 int frontiers_dev(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm, int32_t* labels,
                   vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
+// view.hip: the view gain of n_views cells of an nx x ny grid (host grid in, or null: the plane the last vg_occupancy
+// left on the device; the records, seen (or null) and the summary out); synchronous on the context stream, which the
+// caller drained. Arguments: checked by the caller
+int view_gain_dev(vg_ctx* ctx, const int8_t* grid, const vg_view_params* prm, const int32_t* views, int n_views,
+                  vg_view_rec* recs, int32_t* seen, vg_view_summary* out);
 // change.hip: the change layer's device side. The caller holds the owner's change_mu and has drained ctx's stream
 int change_alloc(vg_ctx* owner, ChangeLayer* L, int hash_log2);
 int change_clear_dev(vg_ctx* ctx, ChangeLayer* L);
@@ -1170,6 +1187,9 @@ int host_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len
 // frontier_host.cpp: the call behind the C-ABI
 int host_frontiers(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg_frontier_params* prm, int32_t* labels,
                    vg_frontier_rec* recs, int max_records, vg_frontier_summary* out);
+// view_host.cpp: the call behind the C-ABI
+int host_view_gain(vg_ctx* ctx, const int8_t* grid, const vg_view_params* prm, const int32_t* views, int n_views,
+                   vg_view_rec* recs, int32_t* seen, vg_view_summary* out);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

@@ -17,7 +17,8 @@
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
 //         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
 //          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]
-//           [--plan "gx gy" [--from "sx sy"] --path out.csv] [--frontiers out.csv]]]]
+//           [--plan "gx gy" [--from "sx sy"] --path out.csv] [--frontiers out.csv
+//           [--view-gain g.csv --view-radius METRES [--view-max-unknown N]]]]]]
 // --checkpoint-out / --checkpoint-at: save a checkpoint (vg_checkpoint_save) once N packages have
 // been stepped, beside it FILE.meta with N; --resume: load FILE before the first package and drop
 // the packages it had consumed (the log is still read from its start: it feeds the synchroniser).
@@ -70,6 +71,12 @@
 // the plan's field reaches, ranked by it. One label,size,cx,cy,best_x,best_y,best_pot row per frontier in the
 // order to visit them (cx, cy: the world centroid; best_x, best_y: the cheapest cell's centre, nan without
 // --plan), and one line on stdout: frontiers: N kept of M, K cells.
+// --view-gain g.csv --view-radius METRES (with --frontiers and --plan): what a 2-D sensor of that range, rounded to
+// whole cells, sees of the grid from every frontier's best cell (NodeCore::frontier_gain: vg_view_gain with grid ==
+// NULL; --view-max-unknown N ends a ray at its N-th unknown cell). One
+// label,best_x,best_y,best_pot,n_unknown,n_free,n_occupied,n_rays_open row per frontier that shows an unknown cell,
+// in the order of the gain per cost (LioCore::ViewGain::order over best_pot), and one line on stdout: view gain: N
+// of M frontiers, radius R cells, K unknown cells in view. out.csv is what it is without these options.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -83,9 +90,9 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
   std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix, plan_s, from_s,
-      plan_csv, fr_csv;
-  double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0;
-  int ck_at = -1;
+      plan_csv, fr_csv, vg_csv;
+  double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0, view_radius = 0.0;
+  int ck_at = -1, view_max_unknown = 0;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
   double places_step = 1.0;
   for (int i = 0; i < argc0; i++) {
@@ -106,6 +113,9 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--from") from_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--path") plan_csv = argv0[++i];
     else if (i + 1 < argc0 && a == "--frontiers") fr_csv = argv0[++i];
+    else if (i + 1 < argc0 && a == "--view-gain") vg_csv = argv0[++i];
+    else if (i + 1 < argc0 && a == "--view-radius") view_radius = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--view-max-unknown") view_max_unknown = atoi(argv0[++i]);
     else if (i + 1 < argc0 && a == "--inscribed") cm_inscribed = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--inflation") cm_inflation = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--cost-scaling") cm_scaling = atof(argv0[++i]);
@@ -139,6 +149,11 @@ int main(int argc0, char** argv0) {
   }
   if (!fr_csv.empty() && cm_prefix.empty()) {
     fprintf(stderr, "%s: --frontiers FILE needs --costmap CPREFIX\n", argv0[0]);
+    return 2;
+  }
+  if ((!vg_csv.empty() || view_radius != 0.0 || view_max_unknown != 0) &&
+      (vg_csv.empty() || fr_csv.empty() || plan_s.empty() || !(view_radius > 0.0) || view_max_unknown < 0)) {
+    fprintf(stderr, "%s: --view-gain FILE needs --frontiers FILE, --plan and a positive --view-radius METRES; --view-max-unknown N >= 0\n", argv0[0]);
     return 2;
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
@@ -475,6 +490,36 @@ int main(int argc0, char** argv0) {
           }
           printf("frontiers: %lld kept of %lld, %lld cells\n", (long long)fs.summary.n_kept,
                  (long long)fs.summary.n_components, (long long)fs.summary.n_frontier_cells);
+          if (!vg_csv.empty()) {
+            FILE* fv = fopen(vg_csv.c_str(), "w");
+            if (!fv) {
+              perror("view-gain");
+              return 1;
+            }
+            size_t rows = 0;
+            long long in_view = 0;
+            int radius = 0;
+            if (!fs.recs.empty()) {  // (vg_view_gain takes at least one viewpoint)
+              const vina_gpu::LioCore::ViewGain vw = node.frontier_gain(fs, view_radius, view_max_unknown);
+              for (const int k : vw.order(vina_gpu::NodeCore::frontier_pots(fs))) {
+                const vg_frontier_rec& r = fs.recs[(size_t)k];
+                const vg_view_rec& v = vw.recs[(size_t)k];
+                double best[2];
+                node.cell_xy(r.best_cell, best);
+                fprintf(fv, "%d,%.17g,%.17g,%u,%d,%d,%d,%d\n", r.label, best[0], best[1], r.best_pot, v.n_unknown, v.n_free,
+                        v.n_occupied, v.n_rays_open);
+                rows++;
+              }
+              in_view = (long long)vw.summary.unknown_seen;
+              radius = (int)(vw.summary.n_ok ? vw.summary.rays / vw.summary.n_ok / 8 : 0);
+            }
+            if (fclose(fv) != 0) {
+              perror("view-gain");
+              return 1;
+            }
+            printf("view gain: %zu of %zu frontiers, radius %d cells, %lld unknown cells in view\n", rows, fs.recs.size(),
+                   radius, in_view);
+          }
         }
       }
       if (!occ_rays.empty()) {

@@ -5,6 +5,7 @@ loads ONLY the in-tree HIP library; there is no CPU fallback — if the library
 or a GPU is missing every call raises.
 """
 import ctypes
+import functools
 import math
 import os
 import re
@@ -208,7 +209,34 @@ FRONTIER_REC = np.dtype([("label", "<i4"), ("size", "<i4"), ("x_min", "<i4"), ("
                          ("y_max", "<i4"), ("sum_x", "<i8"), ("sum_y", "<i8"), ("best_cell", "<i4"), ("best_pot", "<u4"),
                          ("reserved", "<i8", (2,))])
 FRONTIER_MAX_RECORDS = 65536
-NAV_SAT, NAV_UNREACHED = 0xFFFFFFFE, 0xFFFFFFFF
+
+
+class ViewParams(ctypes.Structure):
+    """vg_view_params, 56 bytes."""
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("radius", ctypes.c_int), ("max_unknown", ctypes.c_int),
+                ("flags", ctypes.c_int), ("pad", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class ViewRec(ctypes.Structure):
+    """vg_view_rec, 32 bytes (VIEW_REC is the same layout as a numpy dtype)."""
+    _fields_ = [("ix", ctypes.c_int32), ("iy", ctypes.c_int32), ("status", ctypes.c_int32), ("n_visible", ctypes.c_int32),
+                ("n_unknown", ctypes.c_int32), ("n_free", ctypes.c_int32), ("n_occupied", ctypes.c_int32),
+                ("n_rays_open", ctypes.c_int32)]
+
+
+class ViewSummary(ctypes.Structure):
+    """vg_view_summary, 128 bytes."""
+    _fields_ = [("n_views", ctypes.c_int64), ("n_ok", ctypes.c_int64), ("n_outside", ctypes.c_int64),
+                ("n_blocked", ctypes.c_int64), ("rays", ctypes.c_int64), ("max_unknown_seen", ctypes.c_int64),
+                ("best_view", ctypes.c_int64), ("cells_seen", ctypes.c_int64), ("unknown_seen", ctypes.c_int64),
+                ("reserved", ctypes.c_int64 * 7)]
+
+
+VIEW_REC = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("status", "<i4"), ("n_visible", "<i4"), ("n_unknown", "<i4"),
+                     ("n_free", "<i4"), ("n_occupied", "<i4"), ("n_rays_open", "<i4")])
+VIEW_MAX_RADIUS = 255
+VIEW_OK, VIEW_OUTSIDE, VIEW_BLOCKED = 0, 1, 2
+NAV_SAT,NAV_UNREACHED = 0xFFFFFFFE, 0xFFFFFFFF
 NAV_K_ORTHO, NAV_K_DIAG = 12, 17
 NAV_MAX_POINTS, NAV_MAX_PATH_CELLS = 65536, 1 << 27
 NAV_REACHED, NAV_NO_PATH, NAV_TRUNCATED, NAV_STUCK = 0, 1, 2, 3
@@ -304,6 +332,30 @@ def frontier_order(recs):
     if r.size and (r["best_cell"] >= 0).all():
         return np.lexsort((r["label"], r["best_pot"]))
     return np.lexsort((r["label"], -r["size"].astype(np.int64)))
+
+
+def view_order(view_recs, pots=None, min_gain=1):
+    """The indices of the view records (VIEW_REC) worth visiting, best first: those with status VIEW_OK and
+    n_unknown >= min_gain. With pots (uint32 per record, e.g. the frontier records' best_pot) a comes before b when
+    n_unknown_a (pot_b + 1) > n_unknown_b (pot_a + 1), the gain per cost in exact integers (the products stay
+    below 2^50); ties go to the smaller pot, then the smaller index. Without pots: by descending n_unknown, then
+    index."""
+    r = np.asarray(view_recs)
+    keep = [int(i) for i in np.flatnonzero((r["status"] == VIEW_OK) & (r["n_unknown"] >= min_gain))]
+    gain = [int(v) for v in r["n_unknown"]]
+    if pots is None:
+        return np.array(sorted(keep, key=lambda i: (-gain[i], i)), dtype=np.int64)
+    pot = [int(v) for v in np.asarray(pots, dtype=np.uint32).reshape(-1)]
+    if len(pot) != len(gain):
+        raise ValueError("view_order: one pot per record")
+
+    def cmp(a, b):
+        lhs, rhs = gain[a] * (pot[b] + 1), gain[b] * (pot[a] + 1)
+        if lhs != rhs:
+            return -1 if lhs > rhs else 1
+        return -1 if (pot[a], a) < (pot[b], b) else 1
+
+    return np.array(sorted(keep, key=functools.cmp_to_key(cmp)), dtype=np.int64)
 
 
 def cells_to_world(cells, nx, x0, y0, res):
@@ -623,6 +675,11 @@ def lib():
                                        ctypes.POINTER(FrontierSummary)]
             L.vgx_frontier_ms.argtypes = [P, dp]
             L.vgx_frontier_combine.argtypes = [P, ctypes.c_int]
+        L.has_view_gain = hasattr(L, "vg_view_gain")  # a build older than the view gain (A/B runs)
+        if L.has_view_gain:
+            L.vg_view_gain.argtypes = [P, P, ctypes.POINTER(ViewParams), P, ctypes.c_int, P, P, ctypes.POINTER(ViewSummary)]
+            L.vgx_view_ms.argtypes = [P, dp]
+            L.vgx_view_stage.argtypes = [P, ctypes.c_int]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -1191,6 +1248,41 @@ class Context:
         """Device time (ms) of the last frontiers() call's kernels."""
         ms = ctypes.c_double(0)
         self._chk(lib().vgx_frontier_ms(self.h, ctypes.byref(ms)), "vgx_frontier_ms")
+        return ms.value
+
+    # ---- view gain (vina_gpu.h "View gain")
+    def view_gain(self, views, radius, grid=None, *, nx=None, ny=None, max_unknown=0, want_seen=False):
+        """vg_view_gain from the cells `views` ((n, 2) int32 of ix, iy) of grid (int8 [ny, nx] of OCC_*; None: the
+        grid the last occupancy() call on this context left on the device, nx and ny naming its shape): what a 2-D
+        sensor of range `radius` cells sees from each; max_unknown > 0 ends a ray at that many unknown cells.
+        Returns (the records as a VIEW_REC array, one per viewpoint in the order given; seen int32 [ny, nx], the
+        OK viewpoints that see each cell, or None without want_seen; the summary as a dict)."""
+        if not lib().has_view_gain:
+            raise VgError("this libvina_gpu.so has no view gain (vg_view_gain): rebuild it")
+        g = None
+        if grid is not None:
+            g = np.ascontiguousarray(grid, dtype=np.int8)
+            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
+                raise ValueError("view_gain: grid is [ny, nx]")
+            ny, nx = g.shape
+        elif nx is None or ny is None:
+            raise ValueError("view_gain: grid=None needs nx and ny")
+        v = np.ascontiguousarray(views, dtype=np.int32).reshape(-1, 2)
+        p = ViewParams()
+        p.nx, p.ny, p.radius, p.max_unknown = int(nx), int(ny), int(radius), int(max_unknown)
+        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        seen = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.int32) if want_seen else None
+        recs = np.zeros(max(v.shape[0], 1), dtype=VIEW_REC)
+        s = ViewSummary()
+        self._chk(lib().vg_view_gain(self.h, None if g is None else g.ctypes.data, ctypes.byref(p), v.ctypes.data,
+                                     v.shape[0], recs.ctypes.data, None if seen is None else seen.ctypes.data,
+                                     ctypes.byref(s)), "vg_view_gain")
+        return recs[:v.shape[0]], seen, {f: int(getattr(s, f)) for f, _ in ViewSummary._fields_ if f != "reserved"}
+
+    def view_gain_ms(self):
+        """Device time (ms) of the last view_gain() call's kernels."""
+        ms = ctypes.c_double(0)
+        self._chk(lib().vgx_view_ms(self.h, ctypes.byref(ms)), "vgx_view_ms")
         return ms.value
 
     # ---- the change layer (vina_gpu.h "Change layer")
