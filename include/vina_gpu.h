@@ -637,6 +637,118 @@ typedef struct vg_occ_summary {   /* 128 bytes, no implicit padding */
 int vg_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
                  const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
 
+/* ---- Terrain layer: ground elevation, steps and a ground-relative 2-D grid -------
+ * vg_occupancy's band is relative to each ray's own origin, which is right only
+ * while the sensor keeps one height above one flat floor. vg_terrain casts the
+ * same M origins x D directions twice: first to collect the hits on ground planes
+ * into a per-cell elevation, then to mark obstacle and free relative to the
+ * ground under the ray. It leaves an int8 grid of VG_OCC_* values in the device
+ * slot where vg_occupancy leaves its own (vg_clearance, vg_frontiers and
+ * vg_view_gain with grid == NULL read it). Cells, r_end and which rays mark are
+ * vg_occupancy's: a ray with VG_RAY_TRUNCATED, VG_RAY_LEFT_RANGE or
+ * VG_RAY_INVALID marks nothing in either pass.
+ *
+ * Heights are integers: q(z) = (int64) floor(z / z_res), the division and the
+ * floor in double. |q| >= 2^30 is out of range: such a hit is no ground hit and
+ * adds no n_occ, such a piece is no free piece, and an origin's q(o_z -
+ * sensor_height) is held to +-2^30. clo = q(clear_lo), chi = q(clear_hi) and
+ * smax = q(step_max) are taken once on the host.
+ *
+ * Pass 1, ground. A marking ray with record m, unit direction d and h = o +
+ * m.range d has a ground hit when it hit, d_z < 0, |m.normal[2]| >= up_min, g_lo
+ * <= m.range d_z <= g_hi, q(h_z) is in range and the cell (floor((h_x - x0) /
+ * res), floor((h_y - y0) / res)) lies inside the grid. Each ground hit adds to
+ * four planes with integer atomics: g_n += 1 (int32), g_sum += q(h_z) (int64),
+ * g_min = min(g_min, q(h_z)), g_max = max(g_max, q(h_z)) (int32; INT32_MAX and
+ * INT32_MIN where g_n is 0). A hit of a marking ray whose q(h_z) is out of range
+ * is counted in n_out_of_range, whatever its plane.
+ *
+ * Per cell. elev = floor(g_sum / g_n), the mathematical floor (sums can be
+ * negative), when g_n >= min_ground; else VG_TER_NONE. spread = g_max - g_min, 0
+ * when g_n is 0 (the summary's max_spread only). step[i] = max |elev[i] -
+ * elev[j]| over the 8-neighbours j inside the grid with elev[j] != VG_TER_NONE; 0
+ * when elev[i] is VG_TER_NONE or no neighbour has an elevation. The range of q
+ * keeps spread and step inside int32.
+ *
+ * Pass 2, marks. Every marking ray is traced again and walks the lattice as in
+ * vg_occupancy (the same pieces of positive length, a cell at most once) over
+ * the whole open interval (max(t_min, 0), r_end), with no origin band. It
+ * carries a ground reference ref, first q(o_z - sensor_height). On every piece
+ * (t_in, t_out) in a cell inside the grid, in the order of the walk: where the
+ * cell's elev != VG_TER_NONE, ref becomes that elevation; then the piece is a
+ * free piece when clo <= q(o_z + 0.5 (t_in + t_out) d_z) - ref <= chi. After the
+ * walk the hit is judged against elev of its own cell where that exists, else
+ * against the ref the walk ended with (the last ground the ray passed over: what
+ * stands under a wall's base cell that no ray sees into): it is in band when clo
+ * <= q(h_z) - that reference <= chi. An in-band hit inside the grid adds 1 to
+ * n_occ of its cell. Every free piece adds 1 to n_free of its cell, except in
+ * the in-band hit's own cell (that cell's free mark waits until the hit is
+ * judged). A ray with d_x = d_y = 0 marks only the cell it stands in. flags bit
+ * 0: a ray with VG_RAY_OCCUPIED makes no free mark; it still carries ref and
+ * marks its hit.
+ *
+ * Per cell, vg_occupancy's rule on n_free and n_occ first; then with flags bit 1
+ * a cell with elev != VG_TER_NONE and step > smax becomes VG_OCC_OCCUPIED.
+ *
+ * One elevation per cell: a bridge over a road keeps the level inside the ground
+ * band. Each ray is traced twice, the price of needing the whole elevation
+ * before any mark. */
+#define VG_TER_NONE INT32_MIN   /* elev where the cell has fewer than min_ground ground hits */
+typedef struct vg_terrain_params {   /* 224 bytes, no implicit padding */
+  vg_ray_params ray;        /* as vg_raycast; zero fields: its defaults */
+  double x0, y0;            /* as vg_occ_params */
+  double res;               /* as vg_occ_params */
+  int    nx, ny;            /* as vg_occ_params */
+  double free_on_miss;      /* as vg_occ_params */
+  int    min_occ;           /* <= 0: 1 */
+  int    min_free;          /* <= 0: 1 */
+  double occ_ratio;         /* <= 0: off */
+  int    flags;             /* bit 0: a ray with VG_RAY_OCCUPIED marks no free cell; bit 1: the step rule */
+  int    min_ground;        /* ground hits a cell needs for an elevation; <= 0: 1 */
+  double z_res;             /* the height quantum, metres; <= 0: 0.001; finite */
+  double up_min;            /* a plane is ground when |normal[2]| >= up_min; <= 0: 0.8191520442889918 (cos 35 deg) */
+  double g_lo, g_hi;        /* a ground hit's height relative to its ray's origin, g_lo <= range d_z <= g_hi;
+                               both 0: -3.0 and -0.1; else g_lo < g_hi */
+  double clear_lo, clear_hi;/* the band above the ground in which a hit is an obstacle and a crossed cell is
+                               known free; both 0: 0.15 and 1.5; else clear_lo < clear_hi */
+  double sensor_height;     /* ref before any elevation is met is q(o_z - sensor_height); finite, >= 0 */
+  double step_max;          /* flags bit 1: the largest step that stays passable, metres; finite, >= 0 */
+  double reserved[4];
+} vg_terrain_params;
+typedef struct vg_terrain_summary {   /* 128 bytes, no implicit padding */
+  int64_t n_rays, n_hits, n_hits_in_band, n_truncated, n_occupied_unknown, n_invalid;
+                                          /* as vg_occ_summary; in band: pass 2's, of rays that mark */
+  int64_t n_ground_hits, n_out_of_range;  /* the sum of g_n; hits of marking rays with q(h_z) out of range */
+  int64_t cells_ground;                   /* cells with elev != VG_TER_NONE */
+  int32_t max_step, max_spread;           /* over all cells */
+  int64_t cells_step_lethal;              /* flags bit 1: cells with an elevation and step > smax; else 0 */
+  int64_t free_marks, occ_marks;          /* sums of the two count planes */
+  int64_t cells_free, cells_occupied, cells_unknown;   /* of the grid as returned */
+} vg_terrain_summary;
+/* positions, M, dirs, D, grid: as vg_occupancy. elev, step (nx ny int32 each) and
+ * counts (2 nx ny int32, n_free then n_occ) may each be NULL: that output is not
+ * copied out. Every sum is an integer atomic and min and max commute: no output
+ * depends on the order of the origins, on how M is walked in slabs or on the
+ * calling context. The four ground planes of two calls over a split of the
+ * origins combine to those of one (add, add, min, max). The counts, elev, step
+ * and the grid of two such calls do not: pass 2 of a call reads the elevation of
+ * that call's own ground hits, so every origin whose rays should share a ground
+ * goes into one call. Only the outputs asked
+ * for and the summary leave the device. M == 0 gives an all-unknown grid and
+ * elev all VG_TER_NONE. vg_occupancy's argument errors; z_res, up_min,
+ * sensor_height or (flags bit 1) step_max not finite; sensor_height or step_max
+ * negative; g_lo, g_hi not both 0 and g_lo < g_hi not true; the same of
+ * clear_lo, clear_hi; flags with a bit above 1: VG_E_ARG. Legal where vg_raycast
+ * is; unsharded contexts only (VG_E_STATE with world > 1).
+ *
+ * The four ground planes are not an output of this call. Tests and tools reach
+ * them through two hooks the library exports beside it (not part of the stable
+ * interface, as every vgx_ symbol): vgx_ter_ground copies the last call's planes
+ * out (given that call's nx, ny), vgx_ter_cells runs the per-cell stage alone on planes it is given. */
+int vg_terrain(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
+               const vg_terrain_params* prm, int8_t* grid, int32_t* elev, int32_t* step, int32_t* counts,
+               vg_terrain_summary* out);
+
 /* ---- Clearance field and costmap: what a planner needs of the 2-D grid ---------
  * The exact Euclidean distance transform of an nx x ny grid of VG_OCC_* cells,
  * its feature transform, and nav2's inflation-layer cost of the distance, all on
@@ -691,9 +803,10 @@ typedef struct vg_clr_summary {   /* 128 bytes, no implicit padding */
   int64_t max_dist2;                      /* the largest dist2 of any cell; 0 when O is empty */
   int64_t reserved[8];
 } vg_clr_summary;
-/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call
- * on this context left on the device, of which nothing is uploaded (VG_E_STATE
- * when there was no such call or its nx, ny differ from prm's). dist2, nearest
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy or
+ * vg_terrain call on this context left on the device (both write the same slot),
+ * of which nothing is uploaded (VG_E_STATE when there was no such call or its nx,
+ * ny differ from prm's). dist2, nearest
  * (nx ny int32 each) and cost (nx ny uint8) may each be NULL: that output is not
  * copied out. The planes are device buffers allocated on first use and re-used;
  * only the outputs asked for and the summary leave the device. NULL ctx, prm or
@@ -853,8 +966,8 @@ static_assert(sizeof(vg_frontier_params) == 56 && sizeof(vg_frontier_rec) == 64 
 _Static_assert(sizeof(vg_frontier_params) == 56 && sizeof(vg_frontier_rec) == 64 && sizeof(vg_frontier_summary) == 128,
                "the frontier records have no implicit padding");
 #endif
-/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call on
- * this context left on the device (VG_E_STATE when there was no such call or its nx,
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy or
+ * vg_terrain call on this context left on the device (VG_E_STATE when there was no such call or its nx,
  * ny differ from prm's). cost: consulted only with flags bit 0; nx ny uint8 on the
  * host, or NULL: the plane that the last vg_clearance call on this context left on
  * the device (VG_E_STATE when no call produced one or its nx, ny differ). With
@@ -942,8 +1055,8 @@ static_assert(sizeof(vg_view_params) == 56 && sizeof(vg_view_rec) == 32 && sizeo
 _Static_assert(sizeof(vg_view_params) == 56 && sizeof(vg_view_rec) == 32 && sizeof(vg_view_summary) == 128,
                "the view records have no implicit padding");
 #endif
-/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy call on
- * this context left on the device (VG_E_STATE when there was no such call or its nx,
+/* grid: nx ny int8 on the host, or NULL: the grid that the last vg_occupancy or
+ * vg_terrain call on this context left on the device (VG_E_STATE when there was no such call or its nx,
  * ny differ from prm's). views: n_views pairs (ix, iy), 1 <= n_views <=
  * VG_NAV_MAX_POINTS; recs: one record per viewpoint, in the order given. A cell
  * named twice gets two records and counts twice in seen. seen: nx ny int32, or

@@ -173,6 +173,27 @@ class LioCore {
           "vg_occupancy");
     return r;
   }
+  // the terrain layer (vina_gpu.h "Terrain layer"): the same rays cast twice, for the ground's elevation and then
+  // for a grid judged relative to it; grid as occupancy()'s, left on the device in the same slot; elev (VG_TER_NONE:
+  // none) and step: nx ny heights in units of z_res; counts (with_counts): n_free's plane, then n_occ's
+  struct Terrain {
+    std::vector<int8_t> grid;
+    std::vector<int32_t> elev, step, counts;
+    vg_terrain_summary summary;
+  };
+  Terrain terrain(const double* positions, int M, const double* dirs, int D, const vg_terrain_params& prm,
+                  bool with_counts = false) {
+    Terrain r;
+    const size_t cells = prm.nx > 0 && prm.ny > 0 ? (size_t)prm.nx * (size_t)prm.ny : 1;
+    r.grid.resize(cells <= (size_t)VG_OCC_MAX_CELLS ? cells : 1);
+    r.elev.resize(r.grid.size());
+    r.step.resize(r.grid.size());
+    if (with_counts) r.counts.resize(2 * r.grid.size());
+    check(vg_terrain(ctx_, positions, M, dirs, D, &prm, r.grid.data(), r.elev.data(), r.step.data(),
+                     with_counts ? r.counts.data() : nullptr, &r.summary),
+          "vg_terrain");
+    return r;
+  }
   // the clearance field and costmap (vina_gpu.h "Clearance field and costmap") of grid (nx ny cells of
   // VG_OCC_*; null: the grid the last occupancy() call left on the device); each output is filled only
   // where asked for

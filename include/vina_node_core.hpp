@@ -122,6 +122,54 @@ inline bool write_occupancy_map(const std::string& prefix, const OccupancyGrid& 
           prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), g.res, g.x0, g.y0);
   return fclose(f) == 0;
 }
+// The terrain layer of the node (vina_gpu.h "Terrain layer"): ground elevation, steps and the grid judged
+// relative to the ground
+struct TerrainGridParams {
+  double res = 0.1;      // as OccupancyGridParams
+  double margin = 20.0;  // as OccupancyGridParams
+  int n_az = 360;
+  std::vector<double> elevations_deg = {-30.0, -20.0, -10.0, 0.0, 10.0};  // a fan that reaches the floor
+  vg_terrain_params ter = {};  // sensor_height, bands, thresholds, flags, ray; the grid's fields are filled in
+};
+struct TerrainGrid {
+  double x0 = 0, y0 = 0, res = 0;
+  int nx = 0, ny = 0;
+  std::vector<int8_t> data;        // VG_OCC_*, row-major, cell (ix, iy) at iy nx + ix
+  std::vector<int32_t> elev, step; // heights in units of z_res; elev VG_TER_NONE where there is none
+  vg_terrain_summary summary = {};
+  std::vector<double> origins, dirs;  // what was cast: M x 3, D x 3
+  vg_terrain_params params = {};      // ... with these parameters
+  double z_res() const { return params.z_res > 0.0 ? params.z_res : 0.001; }
+  OccupancyGrid grid() const {        // the grid with its geometry, as occupancy_grid() would return it
+    OccupancyGrid g;
+    g.x0 = x0, g.y0 = y0, g.res = res, g.nx = nx, g.ny = ny;
+    g.data = data;
+    return g;
+  }
+};
+// write_occupancy_map's pair for the grid, and the elevation beside it: prefix.elev (nx ny little-endian int32, row
+// iy = 0 first) and prefix.elev.yaml (data, nx, ny, resolution, origin, z_res, none)
+inline bool write_terrain_map(const std::string& prefix, const TerrainGrid& g) {
+  if (!write_occupancy_map(prefix, g.grid())) return false;
+  FILE* f = fopen((prefix + ".elev").c_str(), "wb");
+  if (!f) return false;
+  for (const int32_t e : g.elev) {
+    const uint32_t u = (uint32_t)e;
+    const unsigned char b[4] = {(unsigned char)u, (unsigned char)(u >> 8), (unsigned char)(u >> 16), (unsigned char)(u >> 24)};
+    if (fwrite(b, 1, 4, f) != 4) {
+      fclose(f);
+      return false;
+    }
+  }
+  if (fclose(f) != 0) return false;
+  const size_t slash = prefix.find_last_of('/');
+  f = fopen((prefix + ".elev.yaml").c_str(), "w");
+  if (!f) return false;
+  fprintf(f, "data: %s.elev\nnx: %d\nny: %d\nresolution: %.17g\norigin: [%.17g, %.17g, 0]\nz_res: %.17g\nnone: %d\n",
+          prefix.substr(slash == std::string::npos ? 0 : slash + 1).c_str(), g.nx, g.ny, g.res, g.x0, g.y0, g.z_res(),
+          (int)VG_TER_NONE);
+  return fclose(f) == 0;
+}
 // The costmap of an OccupancyGrid (nav2's inflation layer; vina_gpu.h "Clearance field and costmap"), with the
 // grid's geometry
 struct Costmap {
@@ -426,37 +474,11 @@ class NodeCore {
   OccupancyGrid occupancy_grid(const OccupancyGridParams& P = OccupancyGridParams()) {
     finish();
     OccupancyGrid g;
-    if (!(P.res > 0.0) || !(P.margin >= 0.0) || P.n_az < 1 || P.elevations_deg.empty())
-      throw Error(VG_E_ARG, "occupancy_grid: res, margin, n_az or the elevations");
-    double lo[2] = {0, 0}, hi[2] = {0, 0};
-    for (const PoseStamped& s : path_) {
-      double o[3];
-      for (int j = 0; j < 3; j++)
-        o[j] = s.p[j] + s.R[3 * j] * cfg_.ext_t[0] + s.R[3 * j + 1] * cfg_.ext_t[1] + s.R[3 * j + 2] * cfg_.ext_t[2];
-      const size_t m = g.origins.size();
-      if (m && std::hypot(std::hypot(o[0] - g.origins[m - 3], o[1] - g.origins[m - 2]), o[2] - g.origins[m - 1]) < P.res)
-        continue;
-      for (int j = 0; j < 2; j++) {
-        lo[j] = m && lo[j] < o[j] ? lo[j] : o[j];
-        hi[j] = m && hi[j] > o[j] ? hi[j] : o[j];
-      }
-      g.origins.insert(g.origins.end(), o, o + 3);
-    }
-    if (g.origins.empty()) throw Error(VG_E_STATE, "occupancy_grid: the path is empty");
-    for (const double e : P.elevations_deg)
-      for (int a = 0; a < P.n_az; a++) {
-        const double az = 2.0 * M_PI * a / P.n_az, el = e * M_PI / 180.0;
-        const double d[3] = {std::cos(el) * std::cos(az), std::cos(el) * std::sin(az), std::sin(el)};
-        g.dirs.insert(g.dirs.end(), d, d + 3);
-      }
     vg_occ_params q = P.occ;
     if (!(q.z_lo < q.z_hi)) q.z_lo = -0.3, q.z_hi = 1.0;
     if (!(q.ray.t_max > 0.0) && P.margin > 0.0) q.ray.t_max = P.margin;
-    const double kx = std::floor((lo[0] - P.margin) / P.res), ky = std::floor((lo[1] - P.margin) / P.res);
-    const double nx = std::ceil((hi[0] + P.margin) / P.res) - kx, ny = std::ceil((hi[1] + P.margin) / P.res) - ky;
-    if (!(nx * ny <= (double)VG_OCC_MAX_CELLS)) throw Error(VG_E_ARG, "occupancy_grid: more than 2^24 cells");
-    q.x0 = g.x0 = kx * P.res, q.y0 = g.y0 = ky * P.res, q.res = g.res = P.res;
-    q.nx = g.nx = nx < 1.0 ? 1 : (int)nx, q.ny = g.ny = ny < 1.0 ? 1 : (int)ny;
+    cast_plan("occupancy_grid", P.res, P.margin, P.n_az, P.elevations_deg, g.origins, g.dirs, g.x0, g.y0, g.nx, g.ny);
+    q.x0 = g.x0, q.y0 = g.y0, q.res = g.res = P.res, q.nx = g.nx, q.ny = g.ny;
     LioCore::Occupancy r = lio_.occupancy(g.origins.data(), (int)(g.origins.size() / 3), g.dirs.data(),
                                           (int)(g.dirs.size() / 3), q);
     g.data = std::move(r.grid);
@@ -465,9 +487,32 @@ class NodeCore {
     return g;
   }
 
+  // The terrain layer cast from the node's own path (vg_terrain): occupancy_grid()'s origins, fan construction and
+  // grid, with a fan that looks down. sensor_height is P.ter's: the sensor's height over the ground it drives on is
+  // a property of the vehicle, not guessed from the first hits. g.grid() is an OccupancyGrid with the same geometry,
+  // and the grid lies on the device where occupancy_grid() leaves its own: costmap(g.grid(), ..., true) prices it.
+  // Completes outstanding work.
+  TerrainGrid terrain_grid(const TerrainGridParams& P = TerrainGridParams()) {
+    finish();
+    TerrainGrid g;
+    vg_terrain_params q = P.ter;
+    if (!(q.ray.t_max > 0.0) && P.margin > 0.0) q.ray.t_max = P.margin;
+    cast_plan("terrain_grid", P.res, P.margin, P.n_az, P.elevations_deg, g.origins, g.dirs, g.x0, g.y0, g.nx, g.ny);
+    q.x0 = g.x0, q.y0 = g.y0, q.res = g.res = P.res, q.nx = g.nx, q.ny = g.ny;
+    LioCore::Terrain r = lio_.terrain(g.origins.data(), (int)(g.origins.size() / 3), g.dirs.data(),
+                                      (int)(g.dirs.size() / 3), q);
+    g.data = std::move(r.grid);
+    g.elev = std::move(r.elev);
+    g.step = std::move(r.step);
+    g.summary = r.summary;
+    g.params = q;
+    return g;
+  }
+
   // The costmap of g (vg_clearance): cost and dist2 with g's geometry. inscribed, inflation: metres; scaling:
-  // 1/m; flags bit 0: unknown cells are obstacles too. on_device: g is what occupancy_grid() returned last and
-  // no vg_occupancy ran on the context since, so the grid is read where that call left it and nothing is uploaded.
+  // 1/m; flags bit 0: unknown cells are obstacles too. on_device: g is what occupancy_grid() returned last, or
+  // terrain_grid()'s grid() (both leave their grid in the same device slot), and neither vg_occupancy nor vg_terrain
+  // ran on the context since, so the grid is read where that call left it and nothing is uploaded.
   // Completes outstanding work.
   Costmap costmap(const OccupancyGrid& g, double inscribed, double inflation, double scaling, int flags = 0,
                   bool on_device = false) {
@@ -653,6 +698,40 @@ class NodeCore {
   LioCore& lio() { return lio_; }
 
  private:
+  // What occupancy_grid() and terrain_grid() cast: the sensor origins of path()'s rows thinned to one per res, the
+  // fan of n_az azimuths at each elevation, and the grid over the origins' bounds grown by margin
+  void cast_plan(const char* who, double res, double margin, int n_az, const std::vector<double>& elevations_deg,
+                 std::vector<double>& origins, std::vector<double>& dirs, double& x0, double& y0, int& gnx, int& gny) {
+    if (!(res > 0.0) || !(margin >= 0.0) || n_az < 1 || elevations_deg.empty())
+      throw Error(VG_E_ARG, std::string(who) + ": res, margin, n_az or the elevations");
+    double lo[2] = {0, 0}, hi[2] = {0, 0};
+    for (const PoseStamped& s : path_) {
+      double o[3];
+      for (int j = 0; j < 3; j++)
+        o[j] = s.p[j] + s.R[3 * j] * cfg_.ext_t[0] + s.R[3 * j + 1] * cfg_.ext_t[1] + s.R[3 * j + 2] * cfg_.ext_t[2];
+      const size_t m = origins.size();
+      if (m && std::hypot(std::hypot(o[0] - origins[m - 3], o[1] - origins[m - 2]), o[2] - origins[m - 1]) < res)
+        continue;
+      for (int j = 0; j < 2; j++) {
+        lo[j] = m && lo[j] < o[j] ? lo[j] : o[j];
+        hi[j] = m && hi[j] > o[j] ? hi[j] : o[j];
+      }
+      origins.insert(origins.end(), o, o + 3);
+    }
+    if (origins.empty()) throw Error(VG_E_STATE, std::string(who) + ": the path is empty");
+    for (const double e : elevations_deg)
+      for (int a = 0; a < n_az; a++) {
+        const double az = 2.0 * M_PI * a / n_az, el = e * M_PI / 180.0;
+        const double d[3] = {std::cos(el) * std::cos(az), std::cos(el) * std::sin(az), std::sin(el)};
+        dirs.insert(dirs.end(), d, d + 3);
+      }
+    const double kx = std::floor((lo[0] - margin) / res), ky = std::floor((lo[1] - margin) / res);
+    const double nx = std::ceil((hi[0] + margin) / res) - kx, ny = std::ceil((hi[1] + margin) / res) - ky;
+    if (!(nx * ny <= (double)VG_OCC_MAX_CELLS)) throw Error(VG_E_ARG, std::string(who) + ": more than 2^24 cells");
+    x0 = kx * res, y0 = ky * res;
+    gnx = nx < 1.0 ? 1 : (int)nx, gny = ny < 1.0 ? 1 : (int)ny;
+  }
+
   static constexpr int kImuCap = 4096;
   struct Scan {
     std::vector<float> xyz, inten, time;

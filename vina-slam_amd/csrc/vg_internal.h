@@ -426,6 +426,17 @@ struct OccBufs {
   int nx = 0, ny = 0;      // the grid the last call left in `grid` (0: none yet); vg_clearance's grid == NULL reads it
   KernelTimer t;           // around a launch's kernels; ms: the last call's, summed over its slabs (vgx_occ_ms)
 };
+// vg_terrain planes (terrain.hip), allocated on first use and grown to the largest
+// grid asked for. The origins, the directions, the two count planes and the grid
+// are OccBufs': the call leaves its grid where vg_occupancy leaves its own
+struct TerBufs {
+  DevBuf<int> gn, gmin, gmax;      // cells each: the ground planes g_n, g_min, g_max
+  DevBuf<unsigned long long> gsum; // cells: g_sum (a signed sum in two's complement)
+  DevBuf<int> elev, step;          // cells each
+  DevBuf<unsigned long long> sum;  // kTerSlots: the summary's counts as the kernels index them
+  int nx = 0, ny = 0;              // the grid whose ground planes the last call left (0: none); vgx_ter_ground reads them
+  KernelTimer t[4];                // around k_ter_ground, k_ter_cells, k_ter_marks, k_ter_classify; ms: the last call's (vgx_ter_ms)
+};
 // vg_clearance staging (clearance.hip), allocated on first use and grown to the
 // largest grid asked for (grid.cap cells: when it grows, the other planes go). dist2 /
 // nearest / cost exist only once a call asked for that output
@@ -670,6 +681,7 @@ struct vg_ctx {
   vg::RayBufs ray;           // vg_raycast / vg_scan_diff staging (raycast.hip), allocated on first use
   vg::InfoBufs info;         // vg_localizability / vg_scan_info staging (localizability.hip), allocated on first use
   vg::OccBufs occ;           // vg_occupancy staging and count planes (occupancy.hip), allocated on first use
+  vg::TerBufs ter;           // vg_terrain planes (terrain.hip), allocated on first use
   vg::ClrBufs clr;           // vg_clearance staging and planes (clearance.hip), allocated on first use
   vg::NavBufs nav;           // vg_navfn / vg_nav_paths planes (navfn.hip), allocated on first use
   vg::FrontierBufs fr;       // vg_frontiers planes (frontier.hip), allocated on first use
@@ -1118,6 +1130,11 @@ int scan_info_dev(vg_ctx* ctx, const MP& mp, const float* xyz, int n, const doub
 // summary out; synchronous on the context stream, which the caller drained). prm: checked by the caller
 int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
                   const vg_occ_params* prm, int8_t* grid, int32_t* counts, vg_occ_summary* out);
+// terrain.hip: the terrain layer of M origins x D directions (host arrays in; grid, elev, step, counts (each or
+// null) and summary out; synchronous on the context stream, which the caller drained). prm: checked by the caller
+int terrain_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const double* dirs, int D,
+                const vg_terrain_params* prm, int8_t* grid, int32_t* elev, int32_t* step, int32_t* counts,
+                vg_terrain_summary* out);
 // clearance.hip: the clearance field and costmap of an nx x ny grid (host grid in, or null: the grid the last
 // vg_occupancy left on the device; dist2, nearest, cost (each or null) and summary out; synchronous on the
 // context stream, which the caller drained). prm: checked by the caller; table: the cost by dist2, table_n
@@ -1176,6 +1193,9 @@ int host_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, c
 // occupancy_host.cpp: the call behind the C-ABI
 int host_occupancy(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D, const vg_occ_params* prm,
                    int8_t* grid, int32_t* counts, vg_occ_summary* out);
+// terrain_host.cpp: the call behind the C-ABI
+int host_terrain(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D, const vg_terrain_params* prm,
+                 int8_t* grid, int32_t* elev, int32_t* step, int32_t* counts, vg_terrain_summary* out);
 // clearance_host.cpp: the call behind the C-ABI
 int host_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, int32_t* dist2, int32_t* nearest,
                    uint8_t* cost, vg_clr_summary* out);

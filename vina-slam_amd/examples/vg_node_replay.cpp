@@ -15,7 +15,9 @@
 // usage: vg_node_replay <events.bin> <out_tum.txt> [device [out_path.txt [out_cmap.bin [out_markers.bin]]]]
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
-//         [--changes FILE [--changes-scans FILE]] [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
+//         [--changes FILE [--changes-scans FILE]]
+//         [--terrain TPREFIX [--sensor-height H] [--step-max S] [--terrain-rays FILE]]
+//         [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
 //          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]
 //           [--plan "gx gy" [--from "sx sy"] --path out.csv] [--frontiers out.csv
 //           [--view-gain g.csv --view-radius METRES [--view-max-unknown N]]]]]]
@@ -56,7 +58,17 @@
 // (image, resolution, origin: [x0, y0, 0], negate: 0, occupied_thresh: 0.65, free_thresh: 0.196). Leaves
 // without a plane are not obstacles in this grid. --occ-rays FILE: what was cast, int32 M, int32 D, the
 // vg_occ_params used, double origins[3 M], double dirs[3 D], to check the grid against the API.
-// --costmap CPREFIX (with --occupancy): straight after the occupancy call the clearance field of that grid is
+// --terrain TPREFIX (with --localize): the terrain layer cast from the same origins on the same grid
+// (NodeCore::terrain_grid: vg_terrain with a fan of elevations -30 .. 10 degrees; --occ-res R; --sensor-height H
+// metres, the sensor's height over the ground it drives on, default 0; --step-max S metres: cells with a larger
+// step become occupied, flags bit 1). Written: the grid judged relative to the ground as TPREFIX.pgm and
+// TPREFIX.yaml in --occupancy's form, and the elevation as TPREFIX.elev (nx ny little-endian int32 in units of
+// z_res, row iy = 0 first, INT32_MIN where there is none) beside TPREFIX.elev.yaml (data, nx, ny, resolution,
+// origin, z_res, none). It runs after --occupancy's cast where both are given, and --costmap (which goes with
+// either) then prices the terrain grid: the one that lies on the device.
+// --terrain-rays FILE: what was cast, int32 M, int32 D, the vg_terrain_params used, double origins[3 M], double
+// dirs[3 D].
+// --costmap CPREFIX (with --occupancy or --terrain): straight after the last cast the clearance field of that grid is
 // taken where it lies on the device (NodeCore::costmap: vg_clearance with grid == NULL) with the robot's
 // --inscribed r and --inflation R radii in metres (defaults 0.3, 1.0) and --cost-scaling s per metre (default
 // 3.0; nav2's cost_scaling_factor), and its cost written as raw bytes (254 lethal, 253 inscribed, 252 .. 1 the
@@ -90,8 +102,9 @@ static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 int main(int argc0, char** argv0) {
   std::vector<char*> pos;
   std::string ck_out, resume, map_file, guess_s, changes_file, changes_scans, occ_prefix, occ_rays, cm_prefix, plan_s, from_s,
-      plan_csv, fr_csv, vg_csv;
+      plan_csv, fr_csv, vg_csv, ter_prefix, ter_rays;
   double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0, view_radius = 0.0;
+  double ter_height = 0.0, ter_step = -1.0;
   int ck_at = -1, view_max_unknown = 0;
   bool localize = false, scan_diff = false, scan_info = false, global = false;
   double places_step = 1.0;
@@ -109,6 +122,10 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--occ-res") occ_res = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--occ-rays") occ_rays = argv0[++i];
     else if (i + 1 < argc0 && a == "--costmap") cm_prefix = argv0[++i];
+    else if (i + 1 < argc0 && a == "--terrain") ter_prefix = argv0[++i];
+    else if (i + 1 < argc0 && a == "--terrain-rays") ter_rays = argv0[++i];
+    else if (i + 1 < argc0 && a == "--sensor-height") ter_height = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--step-max") ter_step = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--plan") plan_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--from") from_s = argv0[++i];
     else if (i + 1 < argc0 && a == "--path") plan_csv = argv0[++i];
@@ -128,16 +145,20 @@ int main(int argc0, char** argv0) {
   const int argc = (int)pos.size();
   char** argv = pos.data();
   const bool changes = !changes_file.empty();
-  if ((scan_diff || scan_info || changes || !occ_prefix.empty()) && !localize) {
-    fprintf(stderr, "%s: --scan-diff, --scan-info, --changes and --occupancy need --map FILE --localize\n", argv0[0]);
+  if ((scan_diff || scan_info || changes || !occ_prefix.empty() || !ter_prefix.empty()) && !localize) {
+    fprintf(stderr, "%s: --scan-diff, --scan-info, --changes, --occupancy and --terrain need --map FILE --localize\n", argv0[0]);
+    return 2;
+  }
+  if (ter_prefix.empty() ? (!ter_rays.empty() || ter_height != 0.0 || ter_step != -1.0) : (!(ter_height >= 0.0) || (ter_step != -1.0 && !(ter_step >= 0.0)))) {
+    fprintf(stderr, "%s: --terrain-rays, --sensor-height H >= 0 and --step-max S >= 0 go with --terrain TPREFIX\n", argv0[0]);
     return 2;
   }
   if ((!occ_rays.empty() && occ_prefix.empty()) || !(occ_res > 0.0)) {
     fprintf(stderr, "%s: --occ-rays needs --occupancy PREFIX, --occ-res a positive edge\n", argv0[0]);
     return 2;
   }
-  if (!cm_prefix.empty() && (occ_prefix.empty() || !(cm_inscribed >= 0.0) || !(cm_inflation >= cm_inscribed) || !(cm_scaling >= 0.0))) {
-    fprintf(stderr, "%s: --costmap needs --occupancy PREFIX, 0 <= --inscribed <= --inflation and --cost-scaling >= 0\n", argv0[0]);
+  if (!cm_prefix.empty() && ((occ_prefix.empty() && ter_prefix.empty()) || !(cm_inscribed >= 0.0) || !(cm_inflation >= cm_inscribed) || !(cm_scaling >= 0.0))) {
+    fprintf(stderr, "%s: --costmap needs --occupancy PREFIX or --terrain TPREFIX, 0 <= --inscribed <= --inflation and --cost-scaling >= 0\n", argv0[0]);
     return 2;
   }
   double plan_goal[2] = {0, 0}, plan_from[2] = {0, 0};
@@ -421,6 +442,36 @@ int main(int argc0, char** argv0) {
         return 1;
       }
     }
+    // --terrain: after --occupancy's cast, so that the grid left on the device is the terrain's; grid_out: that grid
+    const auto run_terrain = [&](vina_gpu::OccupancyGrid& grid_out) -> bool {
+      vina_gpu::TerrainGridParams tp;
+      tp.res = occ_res;
+      tp.ter.sensor_height = ter_height;
+      if (ter_step >= 0.0) tp.ter.flags |= 2, tp.ter.step_max = ter_step;
+      const vina_gpu::TerrainGrid tg = node.terrain_grid(tp);
+      if (!vina_gpu::write_terrain_map(ter_prefix, tg)) {
+        perror("terrain");
+        return false;
+      }
+      const vg_terrain_summary& sm = tg.summary;
+      fprintf(stderr, "terrain: %d x %d cells of %g m from %d origins x %d directions: %lld ground hits on %lld cells, max step %d, %lld occupied (%lld by their step), %lld free, %lld unknown\n",
+              tg.nx, tg.ny, tg.res, (int)(tg.origins.size() / 3), (int)(tg.dirs.size() / 3), (long long)sm.n_ground_hits,
+              (long long)sm.cells_ground, (int)sm.max_step, (long long)sm.cells_occupied, (long long)sm.cells_step_lethal,
+              (long long)sm.cells_free, (long long)sm.cells_unknown);
+      if (!ter_rays.empty()) {
+        const int32_t md[2] = {(int32_t)(tg.origins.size() / 3), (int32_t)(tg.dirs.size() / 3)};
+        FILE* fr = fopen(ter_rays.c_str(), "wb");
+        if (!fr || fwrite(md, sizeof(md), 1, fr) != 1 || fwrite(&tg.params, sizeof(tg.params), 1, fr) != 1 ||
+            fwrite(tg.origins.data(), sizeof(double), tg.origins.size(), fr) != tg.origins.size() ||
+            fwrite(tg.dirs.data(), sizeof(double), tg.dirs.size(), fr) != tg.dirs.size() || fclose(fr) != 0) {
+          perror("terrain-rays");
+          return false;
+        }
+      }
+      grid_out = tg.grid();
+      return true;
+    };
+    vina_gpu::OccupancyGrid nav;  // the grid --costmap prices: --terrain's where given, else --occupancy's (the last cast: it lies on the device)
     if (!occ_prefix.empty()) {
       vina_gpu::OccupancyGridParams op;
       op.res = occ_res;
@@ -433,95 +484,6 @@ int main(int argc0, char** argv0) {
       fprintf(stderr, "occupancy: %d x %d cells of %g m from %d origins x %d directions: %lld occupied, %lld free, %lld unknown\n",
               og.nx, og.ny, og.res, (int)(og.origins.size() / 3), (int)(og.dirs.size() / 3), (long long)sm.cells_occupied,
               (long long)sm.cells_free, (long long)sm.cells_unknown);
-      if (!cm_prefix.empty()) {
-        const vina_gpu::Costmap cm = node.costmap(og, cm_inscribed, cm_inflation, cm_scaling, 0, true);
-        if (!vina_gpu::write_costmap(cm_prefix, cm)) {
-          perror("costmap");
-          return 1;
-        }
-        const vg_clr_summary& cs = cm.summary;
-        fprintf(stderr, "costmap: inscribed %g m, inflation %g m, scaling %g /m: %lld obstacles, %lld lethal, %lld inscribed, %lld inflated, %lld free, %lld no information; max dist2 %lld\n",
-                cm_inscribed, cm_inflation, cm_scaling, (long long)cs.n_obstacles, (long long)cs.cells_lethal,
-                (long long)cs.cells_inscribed, (long long)cs.cells_inflated, (long long)cs.cells_free,
-                (long long)cs.cells_no_info, (long long)cs.max_dist2);
-        if (!plan_s.empty()) {
-          if (from_s.empty()) {
-            if (node.tum_rows().empty()) {
-              fprintf(stderr, "plan: no pose to start from; give --from\n");
-              return 1;
-            }
-            plan_from[0] = node.tum_rows().back().p[0], plan_from[1] = node.tum_rows().back().p[1];
-          }
-          const vina_gpu::Plan pl = node.plan(plan_goal, plan_from, nullptr, cm.nx * cm.ny < 65536 ? cm.nx * cm.ny : 65536, true);
-          FILE* fp = fopen(plan_csv.c_str(), "w");
-          if (!fp) {
-            perror("path");
-            return 1;
-          }
-          for (size_t k = 0; k < pl.cells.size(); k++)
-            fprintf(fp, "%.17g,%.17g,%u\n", pl.xy[2 * k], pl.xy[2 * k + 1], pl.pot[k]);
-          if (fclose(fp) != 0) {
-            perror("path");
-            return 1;
-          }
-          static const char* const names[] = {"REACHED", "NO_PATH", "TRUNCATED", "STUCK"};
-          printf("plan: %s, %d cells, cost %lld, from %.17g %.17g to %.17g %.17g; %lld of %lld passable cells reached\n",
-                 names[pl.status & 3], (int)pl.cells.size(), (long long)pl.cost, plan_from[0], plan_from[1], plan_goal[0],
-                 plan_goal[1], (long long)pl.summary.cells_reached, (long long)pl.summary.cells_passable);
-        }
-        if (!fr_csv.empty()) {
-          const vina_gpu::LioCore::Frontiers fs = node.frontiers(!plan_s.empty());
-          FILE* ff = fopen(fr_csv.c_str(), "w");
-          if (!ff) {
-            perror("frontiers");
-            return 1;
-          }
-          for (const int k : fs.order()) {
-            const vg_frontier_rec& r = fs.recs[(size_t)k];
-            double best[2] = {NAN, NAN};
-            if (r.best_cell >= 0) node.cell_xy(r.best_cell, best);
-            fprintf(ff, "%d,%d,%.17g,%.17g,%.17g,%.17g,%u\n", r.label, r.size,
-                    cm.x0 + ((double)r.sum_x / r.size + 0.5) * cm.res, cm.y0 + ((double)r.sum_y / r.size + 0.5) * cm.res,
-                    best[0], best[1], r.best_pot);
-          }
-          if (fclose(ff) != 0) {
-            perror("frontiers");
-            return 1;
-          }
-          printf("frontiers: %lld kept of %lld, %lld cells\n", (long long)fs.summary.n_kept,
-                 (long long)fs.summary.n_components, (long long)fs.summary.n_frontier_cells);
-          if (!vg_csv.empty()) {
-            FILE* fv = fopen(vg_csv.c_str(), "w");
-            if (!fv) {
-              perror("view-gain");
-              return 1;
-            }
-            size_t rows = 0;
-            long long in_view = 0;
-            int radius = 0;
-            if (!fs.recs.empty()) {  // (vg_view_gain takes at least one viewpoint)
-              const vina_gpu::LioCore::ViewGain vw = node.frontier_gain(fs, view_radius, view_max_unknown);
-              for (const int k : vw.order(vina_gpu::NodeCore::frontier_pots(fs))) {
-                const vg_frontier_rec& r = fs.recs[(size_t)k];
-                const vg_view_rec& v = vw.recs[(size_t)k];
-                double best[2];
-                node.cell_xy(r.best_cell, best);
-                fprintf(fv, "%d,%.17g,%.17g,%u,%d,%d,%d,%d\n", r.label, best[0], best[1], r.best_pot, v.n_unknown, v.n_free,
-                        v.n_occupied, v.n_rays_open);
-                rows++;
-              }
-              in_view = (long long)vw.summary.unknown_seen;
-              radius = (int)(vw.summary.n_ok ? vw.summary.rays / vw.summary.n_ok / 8 : 0);
-            }
-            if (fclose(fv) != 0) {
-              perror("view-gain");
-              return 1;
-            }
-            printf("view gain: %zu of %zu frontiers, radius %d cells, %lld unknown cells in view\n", rows, fs.recs.size(),
-                   radius, in_view);
-          }
-        }
-      }
       if (!occ_rays.empty()) {
         const int32_t md[2] = {(int32_t)(og.origins.size() / 3), (int32_t)(og.dirs.size() / 3)};
         FILE* fr = fopen(occ_rays.c_str(), "wb");
@@ -530,6 +492,97 @@ int main(int argc0, char** argv0) {
             fwrite(og.dirs.data(), sizeof(double), og.dirs.size(), fr) != og.dirs.size() || fclose(fr) != 0) {
           perror("occ-rays");
           return 1;
+        }
+      }
+      nav = og;
+    }
+    if (!ter_prefix.empty() && !run_terrain(nav)) return 1;
+    if (!cm_prefix.empty()) {
+      const vina_gpu::Costmap cm = node.costmap(nav, cm_inscribed, cm_inflation, cm_scaling, 0, true);
+      if (!vina_gpu::write_costmap(cm_prefix, cm)) {
+        perror("costmap");
+        return 1;
+      }
+      const vg_clr_summary& cs = cm.summary;
+      fprintf(stderr, "costmap: inscribed %g m, inflation %g m, scaling %g /m: %lld obstacles, %lld lethal, %lld inscribed, %lld inflated, %lld free, %lld no information; max dist2 %lld\n",
+              cm_inscribed, cm_inflation, cm_scaling, (long long)cs.n_obstacles, (long long)cs.cells_lethal,
+              (long long)cs.cells_inscribed, (long long)cs.cells_inflated, (long long)cs.cells_free,
+              (long long)cs.cells_no_info, (long long)cs.max_dist2);
+      if (!plan_s.empty()) {
+        if (from_s.empty()) {
+          if (node.tum_rows().empty()) {
+            fprintf(stderr, "plan: no pose to start from; give --from\n");
+            return 1;
+          }
+          plan_from[0] = node.tum_rows().back().p[0], plan_from[1] = node.tum_rows().back().p[1];
+        }
+        const vina_gpu::Plan pl = node.plan(plan_goal, plan_from, nullptr, cm.nx * cm.ny < 65536 ? cm.nx * cm.ny : 65536, true);
+        FILE* fp = fopen(plan_csv.c_str(), "w");
+        if (!fp) {
+          perror("path");
+          return 1;
+        }
+        for (size_t k = 0; k < pl.cells.size(); k++)
+          fprintf(fp, "%.17g,%.17g,%u\n", pl.xy[2 * k], pl.xy[2 * k + 1], pl.pot[k]);
+        if (fclose(fp) != 0) {
+          perror("path");
+          return 1;
+        }
+        static const char* const names[] = {"REACHED", "NO_PATH", "TRUNCATED", "STUCK"};
+        printf("plan: %s, %d cells, cost %lld, from %.17g %.17g to %.17g %.17g; %lld of %lld passable cells reached\n",
+               names[pl.status & 3], (int)pl.cells.size(), (long long)pl.cost, plan_from[0], plan_from[1], plan_goal[0],
+               plan_goal[1], (long long)pl.summary.cells_reached, (long long)pl.summary.cells_passable);
+      }
+      if (!fr_csv.empty()) {
+        const vina_gpu::LioCore::Frontiers fs = node.frontiers(!plan_s.empty());
+        FILE* ff = fopen(fr_csv.c_str(), "w");
+        if (!ff) {
+          perror("frontiers");
+          return 1;
+        }
+        for (const int k : fs.order()) {
+          const vg_frontier_rec& r = fs.recs[(size_t)k];
+          double best[2] = {NAN, NAN};
+          if (r.best_cell >= 0) node.cell_xy(r.best_cell, best);
+          fprintf(ff, "%d,%d,%.17g,%.17g,%.17g,%.17g,%u\n", r.label, r.size,
+                  cm.x0 + ((double)r.sum_x / r.size + 0.5) * cm.res, cm.y0 + ((double)r.sum_y / r.size + 0.5) * cm.res,
+                  best[0], best[1], r.best_pot);
+        }
+        if (fclose(ff) != 0) {
+          perror("frontiers");
+          return 1;
+        }
+        printf("frontiers: %lld kept of %lld, %lld cells\n", (long long)fs.summary.n_kept,
+               (long long)fs.summary.n_components, (long long)fs.summary.n_frontier_cells);
+        if (!vg_csv.empty()) {
+          FILE* fv = fopen(vg_csv.c_str(), "w");
+          if (!fv) {
+            perror("view-gain");
+            return 1;
+          }
+          size_t rows = 0;
+          long long in_view = 0;
+          int radius = 0;
+          if (!fs.recs.empty()) {  // (vg_view_gain takes at least one viewpoint)
+            const vina_gpu::LioCore::ViewGain vw = node.frontier_gain(fs, view_radius, view_max_unknown);
+            for (const int k : vw.order(vina_gpu::NodeCore::frontier_pots(fs))) {
+              const vg_frontier_rec& r = fs.recs[(size_t)k];
+              const vg_view_rec& v = vw.recs[(size_t)k];
+              double best[2];
+              node.cell_xy(r.best_cell, best);
+              fprintf(fv, "%d,%.17g,%.17g,%u,%d,%d,%d,%d\n", r.label, best[0], best[1], r.best_pot, v.n_unknown, v.n_free,
+                      v.n_occupied, v.n_rays_open);
+              rows++;
+            }
+            in_view = (long long)vw.summary.unknown_seen;
+            radius = (int)(vw.summary.n_ok ? vw.summary.rays / vw.summary.n_ok / 8 : 0);
+          }
+          if (fclose(fv) != 0) {
+            perror("view-gain");
+            return 1;
+          }
+          printf("view gain: %zu of %zu frontiers, radius %d cells, %lld unknown cells in view\n", rows, fs.recs.size(),
+                 radius, in_view);
         }
       }
     }

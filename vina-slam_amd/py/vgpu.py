@@ -156,6 +156,27 @@ class OccSummary(ctypes.Structure):
                 ("cells_occupied", ctypes.c_int64), ("cells_unknown", ctypes.c_int64), ("reserved", ctypes.c_int64 * 5)]
 
 
+class TerrainParams(ctypes.Structure):
+    """vg_terrain_params, 224 bytes."""
+    _fields_ = [("ray", RayParams), ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("res", ctypes.c_double),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("free_on_miss", ctypes.c_double),
+                ("min_occ", ctypes.c_int), ("min_free", ctypes.c_int), ("occ_ratio", ctypes.c_double),
+                ("flags", ctypes.c_int), ("min_ground", ctypes.c_int), ("z_res", ctypes.c_double),
+                ("up_min", ctypes.c_double), ("g_lo", ctypes.c_double), ("g_hi", ctypes.c_double),
+                ("clear_lo", ctypes.c_double), ("clear_hi", ctypes.c_double), ("sensor_height", ctypes.c_double),
+                ("step_max", ctypes.c_double), ("reserved", ctypes.c_double * 4)]
+
+
+class TerrainSummary(ctypes.Structure):
+    """vg_terrain_summary, 128 bytes."""
+    _fields_ = [("n_rays", ctypes.c_int64), ("n_hits", ctypes.c_int64), ("n_hits_in_band", ctypes.c_int64),
+                ("n_truncated", ctypes.c_int64), ("n_occupied_unknown", ctypes.c_int64), ("n_invalid", ctypes.c_int64),
+                ("n_ground_hits", ctypes.c_int64), ("n_out_of_range", ctypes.c_int64), ("cells_ground", ctypes.c_int64),
+                ("max_step", ctypes.c_int32), ("max_spread", ctypes.c_int32), ("cells_step_lethal", ctypes.c_int64),
+                ("free_marks", ctypes.c_int64), ("occ_marks", ctypes.c_int64), ("cells_free", ctypes.c_int64),
+                ("cells_occupied", ctypes.c_int64), ("cells_unknown", ctypes.c_int64)]
+
+
 class ClrParams(ctypes.Structure):
     """vg_clr_params, 80 bytes."""
     _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("res", ctypes.c_double), ("flags", ctypes.c_int),
@@ -259,6 +280,50 @@ def occ_params(x0=0.0, y0=0.0, res=0.0, nx=0, ny=0, z_lo=-0.3, z_hi=1.0, free_on
     p.z_lo, p.z_hi, p.free_on_miss = z_lo, z_hi, free_on_miss
     p.min_occ, p.min_free, p.occ_ratio, p.flags = min_occ, min_free, occ_ratio, flags
     return p
+
+
+TER_NONE = -2 ** 31
+
+
+def terrain_params(x0=0.0, y0=0.0, res=0.0, nx=0, ny=0, free_on_miss=0.0, min_occ=0, min_free=0, occ_ratio=0.0,
+                   flags=0, min_ground=0, z_res=0.0, up_min=0.0, g_lo=0.0, g_hi=0.0, clear_lo=0.0, clear_hi=0.0,
+                   sensor_height=0.0, step_max=0.0, **ray):
+    """vg_terrain_params; zeros take the library's defaults (a 1 mm height quantum, planes within 35 degrees of
+    level as ground, ground hits 3 m .. 0.1 m below the sensor, obstacles 0.15 .. 1.5 m above the ground)."""
+    p = TerrainParams()
+    p.ray = ray_params(**ray)
+    p.x0, p.y0, p.res, p.nx, p.ny = x0, y0, res, nx, ny
+    p.free_on_miss, p.min_occ, p.min_free, p.occ_ratio = free_on_miss, min_occ, min_free, occ_ratio
+    p.flags, p.min_ground, p.z_res, p.up_min = flags, min_ground, z_res, up_min
+    p.g_lo, p.g_hi, p.clear_lo, p.clear_hi = g_lo, g_hi, clear_lo, clear_hi
+    p.sensor_height, p.step_max = sensor_height, step_max
+    return p
+
+
+def write_terrain(prefix, elev, x0, y0, res, z_res):
+    """The elevation (int32 [ny, nx], TER_NONE where there is none) as raw little-endian int32 in prefix.elev,
+    row iy first as in memory, beside prefix.elev.yaml with the grid's shape, origin, res and z_res (a
+    height in metres is elev z_res)."""
+    e = np.ascontiguousarray(elev, dtype="<i4")
+    with open(prefix + ".elev", "wb") as f:
+        f.write(e.tobytes())
+    with open(prefix + ".elev.yaml", "w") as f:
+        f.write("data: %s\nnx: %d\nny: %d\nresolution: %r\norigin: [%r, %r, 0]\nz_res: %r\nnone: %d\n"
+                % (os.path.basename(prefix) + ".elev", e.shape[1], e.shape[0], float(res), float(x0), float(y0),
+                   float(z_res), TER_NONE))
+
+
+def read_terrain(prefix):
+    """(elev int32 [ny, nx], x0, y0, res, z_res) back from write_terrain's (or vg_node_replay --terrain's) pair."""
+    meta = {}
+    for ln in open(prefix + ".elev.yaml"):
+        k, _, v = ln.partition(":")
+        meta[k.strip()] = v.strip()
+    org = [float(x) for x in meta["origin"].strip("[]").split(",")]
+    nx, ny = int(meta["nx"]), int(meta["ny"])
+    raw = open(os.path.join(os.path.dirname(prefix), meta["data"]), "rb").read()
+    e = np.frombuffer(raw, dtype="<i4", count=nx * ny).reshape(ny, nx).astype(np.int32)
+    return e, org[0], org[1], float(meta["resolution"]), float(meta["z_res"])
 
 
 def occupancy_dirs(n_az=360, elevations_deg=(-10, 0, 10)):
@@ -660,6 +725,13 @@ def lib():
             L.vg_occupancy.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(OccParams), P, P,
                                        ctypes.POINTER(OccSummary)]
             L.vgx_occ_ms.argtypes = [P, dp]
+        L.has_terrain = hasattr(L, "vg_terrain")  # a build older than the terrain layer (A/B runs)
+        if L.has_terrain:
+            L.vg_terrain.argtypes = [P, dp, ctypes.c_int, dp, ctypes.c_int, ctypes.POINTER(TerrainParams), P, P, P, P,
+                                     ctypes.POINTER(TerrainSummary)]
+            L.vgx_ter_ground.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P, P]
+            L.vgx_ter_cells.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, P, P, P, P]
+            L.vgx_ter_ms.argtypes = [P, dp]
         L.has_clearance = hasattr(L, "vg_clearance")  # a build older than the clearance field (A/B runs)
         if L.has_clearance:
             L.vg_clearance.argtypes = [P, P, ctypes.POINTER(ClrParams), P, P, P, ctypes.POINTER(ClrSummary)]
@@ -1106,6 +1178,60 @@ class Context:
         ms = ctypes.c_double(0)
         self._chk(lib().vgx_occ_ms(self.h, ctypes.byref(ms)), "vgx_occ_ms")
         return ms.value
+
+    # ---- the terrain layer (vina_gpu.h "Terrain layer")
+    def terrain(self, positions, dirs=None, **params):
+        """vg_terrain: ground elevation, steps and the ground-relative grid ray-cast from positions (M, 3) along
+        dirs (D, 3) shared by all of them (None: occupancy_dirs()). params: terrain_params (x0, y0, res, nx, ny and
+        the rest) or prm=a filled TerrainParams. Returns (grid int8 [ny, nx] of OCC_*, elev int32 [ny, nx] (TER_NONE:
+        none), step int32 [ny, nx], counts int32 [2, ny, nx] (n_free, n_occ), the summary as a dict). The grid stays
+        on the device where occupancy() leaves its own."""
+        if not lib().has_terrain:
+            raise VgError("this libvina_gpu.so has no terrain layer (vg_terrain): rebuild it")
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(occupancy_dirs() if dirs is None else dirs, dtype=np.float64).reshape(-1, 3)
+        p = params["prm"] if "prm" in params else terrain_params(**params)   # prm: a filled TerrainParams
+        cells = p.nx * p.ny if 1 <= p.nx and 1 <= p.ny and p.nx * p.ny <= OCC_MAX_CELLS else 1
+        grid = np.zeros(cells, dtype=np.int8)
+        elev, step = np.zeros(cells, dtype=np.int32), np.zeros(cells, dtype=np.int32)
+        cnt = np.zeros(2 * cells, dtype=np.int32)
+        s = TerrainSummary()
+        self._chk(lib().vg_terrain(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0],
+                                   _d(d) if d.shape[0] else None, d.shape[0], ctypes.byref(p), grid.ctypes.data,
+                                   elev.ctypes.data, step.ctypes.data, cnt.ctypes.data, ctypes.byref(s)), "vg_terrain")
+        summ = {f: int(getattr(s, f)) for f, _ in TerrainSummary._fields_}
+        return (grid.reshape(p.ny, p.nx), elev.reshape(p.ny, p.nx), step.reshape(p.ny, p.nx),
+                cnt.reshape(2, p.ny, p.nx), summ)
+
+    def terrain_ground(self, nx, ny):
+        """Test hook (vgx_ter_ground): the four ground planes the last terrain() call left on the device, (g_n
+        int32, g_sum int64, g_min int32, g_max int32), [ny, nx] each; nx, ny other than that call's is refused."""
+        g_n, g_min, g_max = (np.zeros((ny, nx), dtype=np.int32) for _ in range(3))
+        g_sum = np.zeros((ny, nx), dtype=np.int64)
+        self._chk(lib().vgx_ter_ground(self.h, nx, ny, g_n.ctypes.data, g_sum.ctypes.data, g_min.ctypes.data,
+                                       g_max.ctypes.data), "vgx_ter_ground")
+        return g_n, g_sum, g_min, g_max
+
+    def terrain_cells(self, g_n, g_sum, g_min, g_max, min_ground=1):
+        """Test hook (vgx_ter_cells): the per-cell stage alone on ground planes [ny, nx]. Returns (elev, step int32
+        [ny, nx], (cells_ground, max_step, max_spread))."""
+        g_n, g_min, g_max = (np.ascontiguousarray(a, dtype=np.int32) for a in (g_n, g_min, g_max))
+        g_sum = np.ascontiguousarray(g_sum, dtype=np.int64)
+        ny, nx = g_n.shape
+        assert g_sum.shape == g_min.shape == g_max.shape == (ny, nx)
+        elev, step = np.zeros((ny, nx), dtype=np.int32), np.zeros((ny, nx), dtype=np.int32)
+        out = np.zeros(3, dtype=np.int64)
+        self._chk(lib().vgx_ter_cells(self.h, nx, ny, min_ground, g_n.ctypes.data, g_sum.ctypes.data, g_min.ctypes.data,
+                                      g_max.ctypes.data, elev.ctypes.data, step.ctypes.data, out.ctypes.data),
+                  "vgx_ter_cells")
+        return elev, step, tuple(int(v) for v in out)
+
+    def ter_ms(self):
+        """Device time (ms) of the last terrain() call's kernels: (k_ter_ground, k_ter_cells, k_ter_marks,
+        k_ter_classify), the ray kernels summed over their slabs."""
+        ms = (ctypes.c_double * 4)()
+        self._chk(lib().vgx_ter_ms(self.h, ms), "vgx_ter_ms")
+        return tuple(ms)
 
     # ---- the clearance field and costmap (vina_gpu.h "Clearance field and costmap")
     def clearance(self, grid=None, *, nx=None, ny=None, res, flags=0, inscribed_radius=0.0, inflation_radius=0.0,
