@@ -20,6 +20,7 @@
 #include <cstdio>
 #include "ckpt_file.h"
 #include "vg_dev.h"
+#include "vg_reduce.h"
 
 namespace vg {
 namespace {
@@ -64,10 +65,6 @@ __global__ void __launch_bounds__(256) k_ckpt_copy(const CopyDesc* __restrict__ 
 struct SumDesc {
   unsigned long long off, words;  // in the image; 64-bit words (the last one zero-padded in the image)
 };
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 // Section blockIdx.y, partial blockIdx.x: sum of word[i] * (kCkptMul * (2 i + 1))
 // over this workgroup's share, two words per 16-byte load; 64-lane shuffles,
 // one partial per workgroup (no atomics, no last-workgroup ticket)

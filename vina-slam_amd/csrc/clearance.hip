@@ -25,7 +25,8 @@
 // atomics are the summary's integer ones.
 #include <climits>
 
-#include "vg_internal.h"
+#include "vg_query.h"
+#include "vg_reduce.h"
 
 namespace vg {
 
@@ -38,12 +39,6 @@ enum { kClrObstacles = 0, kClrUnknown, kClrLethal, kClrInscribed, kClrInflated, 
 
 __device__ __forceinline__ bool clr_obstacle(int v, int unknown_too) {
   return v == VG_OCC_OCCUPIED || (unknown_too && v == VG_OCC_UNKNOWN);
-}
-
-__device__ __forceinline__ unsigned long long clr_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0's is the wave's)
 }
 
 __global__ void __launch_bounds__(kClrBlock) k_clr_cols(const int8_t* __restrict__ grid, int nx, int ny,
@@ -82,8 +77,8 @@ __global__ void __launch_bounds__(kClrBlock) k_clr_cols(const int8_t* __restrict
       }
     }
   }
-  n_obst = clr_wave_sum(n_obst);
-  n_unk = clr_wave_sum(n_unk);
+  n_obst = wave_sum(n_obst);
+  n_unk = wave_sum(n_unk);
   if ((threadIdx.x & 63) == 0) {
     if (n_obst) atomicAdd(&sum[kClrObstacles], n_obst);
     if (n_unk) atomicAdd(&sum[kClrUnknown], n_unk);
@@ -143,14 +138,10 @@ __global__ void __launch_bounds__(kClrBlock) k_clr_rows(const int8_t* __restrict
   }
 #pragma unroll
   for (int j = 0; j < 5; j++) {
-    const unsigned long long n = clr_wave_sum(n_cls[j]);
+    const unsigned long long n = wave_sum(n_cls[j]);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&sum[kClrLethal + j], n);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_down(d2_max, off, 64);
-    d2_max = o > d2_max ? o : d2_max;
-  }
+  d2_max = wave_max(d2_max);
   if ((threadIdx.x & 63) == 0 && d2_max) atomicMax(&sum[kClrMaxDist2], d2_max);
 }
 
@@ -188,7 +179,7 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
   ClrBufs& b = ctx->clr;
   hipStream_t s = ctx->stream;
   unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
-  const int8_t* d_grid = grid ? b.grid.p : ctx->occ.grid.p;
+  const int8_t* d_grid;
   b.t.clear();
   if (cost) b.nx = b.ny = 0;  // (no cost plane to hand to vg_navfn until this call has finished)
   if (table) {
@@ -200,7 +191,7 @@ int clearance_dev(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, con
     memcpy(b.table_key, key, sizeof(key));
     b.table_n = table_n;
   }
-  if (grid) VG_HIP(hipMemcpyAsync(b.grid, grid, cells, hipMemcpyHostToDevice, s));
+  VG_TRY(plane_in(ctx, grid, b.grid, ctx->occ.grid.p, cells, &d_grid));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_clr_summary), s));
   VG_HIP(b.t.begin(s));
   k_clr_cols<<<(nx + kClrBlock - 1) / kClrBlock, kClrBlock, 0, s>>>(d_grid, nx, ny, prm->flags & 1, b.dy, d_sum);

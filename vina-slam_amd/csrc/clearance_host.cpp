@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "vg_host.h"
+#include "vg_query.h"
 
 namespace vg {
 
@@ -19,22 +20,14 @@ static uint8_t clr_cost(const vg_clr_params* p, long long dist2) {
 
 int host_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, int32_t* dist2, int32_t* nearest,
                    uint8_t* cost, vg_clr_summary* out) {
-  if (ctx->shard.world > 1) {
-    ctx->err = "vg_clearance: the context is sharded (world > 1)";
-    return VG_E_STATE;
-  }
+  VG_TRY(query_open(ctx, "vg_clearance"));
   // entries 0 .. floor((inflation_radius / res)^2), and one more evaluated the same way, so that a dist2 whose d
   // rounds onto the radius is still looked up; past it the cost is 0. No entry beyond the grid's largest dist2
   const double q = (prm->inflation_radius / prm->res) * (prm->inflation_radius / prm->res);
   const long long far = (long long)(prm->nx - 1) * (prm->nx - 1) + (long long)(prm->ny - 1) * (prm->ny - 1);
   const long long want = (long long)std::floor(q) + 2;
   const int table_n = (int)(want < far + 1 ? want : far + 1);
-  VG_TRY(host_quiesce(ctx));
-  if (!grid && (!ctx->occ.grid || ctx->occ.nx != prm->nx || ctx->occ.ny != prm->ny)) {
-    ctx->err = ctx->occ.nx ? "vg_clearance: grid == NULL, and the last vg_occupancy call's nx, ny differ from prm's"
-                           : "vg_clearance: grid == NULL, and no vg_occupancy call left a grid on this context";
-    return VG_E_STATE;
-  }
+  if (!grid) VG_TRY(held_grid_ok(ctx, "vg_clearance", "grid == NULL", prm->nx, prm->ny));
   std::vector<uint8_t> table;
   if (!clr_table_current(ctx, prm, table_n)) {
     table.resize((size_t)table_n);
@@ -48,9 +41,7 @@ int host_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, in
 extern "C" int vg_clearance(vg_ctx* ctx, const int8_t* grid, const vg_clr_params* prm, int32_t* dist2,
                             int32_t* nearest, uint8_t* cost, vg_clr_summary* out) {
   if (!ctx || !prm || !out) return VG_E_ARG;
-  if (prm->nx < 1 || prm->ny < 1 || prm->nx > VG_CLR_MAX_SIDE || prm->ny > VG_CLR_MAX_SIDE ||
-      (long long)prm->nx * (long long)prm->ny > (long long)VG_OCC_MAX_CELLS)
-    return VG_E_ARG;
+  if (!vg::grid_shape_ok(prm->nx, prm->ny, VG_CLR_MAX_SIDE)) return VG_E_ARG;
   if (!(prm->res > 0.0) || !std::isfinite(prm->res)) return VG_E_ARG;
   if (!(prm->inscribed_radius >= 0.0) || !std::isfinite(prm->inscribed_radius) || !std::isfinite(prm->inflation_radius) ||
       !(prm->inflation_radius >= prm->inscribed_radius) || !(prm->cost_scaling >= 0.0) || !std::isfinite(prm->cost_scaling))

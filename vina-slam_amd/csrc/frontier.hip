@@ -62,7 +62,8 @@
 #include <climits>
 #include <cstddef>
 
-#include "vg_internal.h"
+#include "vg_query.h"
+#include "vg_reduce.h"
 
 namespace vg {
 
@@ -80,22 +81,6 @@ enum { kFrCells = 0, kFrComponents, kFrKept, kFrWritten, kFrMaxSize, kFrFree, kF
        kFrFlag = 16, kFrSlots = 17 };
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 fr_wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0's is the wave's)
-}
-__device__ __forceinline__ int fr_wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_down(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int fr_wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_down(v, off, 64));
-  return v;
-}
 
 // ---- the union-find, over LDS (workgroup scope) or global memory (agent scope)
 
@@ -199,11 +184,11 @@ __global__ void __launch_bounds__(kFrBlock) k_fr_tile(const int8_t* __restrict__
     }
     parent[(size_t)(y0 + ly) * nx + x0 + lx] = p;
   }
-  n_front = fr_wave_sum(n_front);
-  n_free = fr_wave_sum(n_free);
-  n_unk = fr_wave_sum(n_unk);
-  n_rc = fr_wave_sum(n_rc);
-  n_ru = fr_wave_sum(n_ru);
+  n_front = wave_sum(n_front);
+  n_free = wave_sum(n_free);
+  n_unk = wave_sum(n_unk);
+  n_rc = wave_sum(n_rc);
+  n_ru = wave_sum(n_ru);
   if ((threadIdx.x & 63) == 0) {
     if (n_front) atomicAdd(&sum[kFrCells], n_front);
     if (n_free) atomicAdd(&sum[kFrFree], n_free);
@@ -340,15 +325,10 @@ __global__ void __launch_bounds__(kFrBlock) k_fr_stats(const int* __restrict__ l
     const int id0 = __shfl(id, __ffsll((unsigned long long)m) - 1, 64);
     if (!__ballot(front && id != id0)) {  // (wave-uniform)
       const int n = __popcll(m);
-      const u64 sx = fr_wave_sum(front ? (u64)x : 0ull), sy = fr_wave_sum(front ? (u64)y : 0ull);
-      const int x_lo = fr_wave_min(front ? x : INT_MAX), y_lo = fr_wave_min(front ? y : INT_MAX);
-      const int x_hi = fr_wave_max(front ? x : -1), y_hi = fr_wave_max(front ? y : -1);
-      u64 best = key;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_down(best, off, 64);
-        best = o < best ? o : best;
-      }
+      const u64 sx = wave_sum(front ? (u64)x : 0ull), sy = wave_sum(front ? (u64)y : 0ull);
+      const int x_lo = wave_min(front ? x : INT_MAX), y_lo = wave_min(front ? y : INT_MAX);
+      const int x_hi = wave_max(front ? x : -1), y_hi = wave_max(front ? y : -1);
+      const u64 best = wave_min(key);
       if ((threadIdx.x & 63) == 0) {
         vg_frontier_rec* r = rec + id0;
         atomicAdd(&r->size, n);
@@ -380,7 +360,7 @@ __global__ void __launch_bounds__(kFrBlock) k_fr_keep(const vg_frontier_rec* __r
   int before;
   const int total = fr_block_rank(size >= min_size, &before);  // (min_size >= 1: a lane past n keeps nothing)
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
-  const int big = fr_wave_max(size);
+  const int big = wave_max(size);
   if ((threadIdx.x & 63) == 0 && big) atomicMax(&sum[kFrMaxSize], (u64)big);
 }
 
@@ -424,13 +404,13 @@ int frontiers_dev(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const vg
   VG_TRY(fr_bufs(ctx, cells));
   if (cost) VG_HIP(b.cost.reserve(cells));
   hipStream_t s = ctx->stream;
-  const int8_t* d_grid = grid ? b.grid.p : ctx->occ.grid.p;
-  const uint8_t* d_cost = !use_cost ? nullptr : cost ? b.cost.p : ctx->clr.cost.p;
+  const int8_t* d_grid;
+  const uint8_t* d_cost;  // (null without the cost test; a host plane comes with use_cost only)
   const unsigned* d_pot = use_pot ? ctx->nav.pot.p : nullptr;
   u64 h_sum[kFrSlots];
   b.t.clear();
-  if (grid) VG_HIP(hipMemcpyAsync(b.grid, grid, cells, hipMemcpyHostToDevice, s));
-  if (cost) VG_HIP(hipMemcpyAsync(b.cost, cost, cells, hipMemcpyHostToDevice, s));
+  VG_TRY(plane_in(ctx, grid, b.grid, ctx->occ.grid.p, cells, &d_grid));
+  VG_TRY(plane_in(ctx, cost, b.cost, use_cost ? ctx->clr.cost.p : nullptr, cells, &d_cost));
   VG_HIP(hipMemsetAsync(b.sum, 0, kFrSlots * sizeof(u64), s));
   VG_HIP(b.t.begin(s));
   k_fr_tile<<<(unsigned)(tiles_x * tiles_y), kFrBlock, 0, s>>>(d_grid, d_cost, d_pot, nx, ny, tiles_x, cost_max, b.parent,

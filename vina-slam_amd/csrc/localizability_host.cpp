@@ -4,26 +4,19 @@
 #include <cstring>
 
 #include "vg_host.h"
+#include "vg_query.h"
 
 namespace vg {
 
-static int info_allowed(vg_ctx* ctx, const char* who) {
-  if (ctx->shard.world > 1) {
-    ctx->err = std::string(who) + ": the context is sharded (world > 1)";
-    return VG_E_STATE;
-  }
-  return host_quiesce(ctx);
-}
-
 int host_localizability(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
                         const vg_info_params* prm, vg_info_rec* out) {
-  VG_TRY(info_allowed(ctx, "vg_localizability"));
+  VG_TRY(query_open(ctx, "vg_localizability"));
   return localizability_dev(ctx, hp(ctx)->mpd, positions, M, dirs, D, prm, out);
 }
 
 int host_scan_info(vg_ctx* ctx, const float* xyz, int n, const double* pose12, const vg_diff_params* diff,
                    const vg_info_params* prm, vg_info_rec* out) {
-  VG_TRY(info_allowed(ctx, "vg_scan_info"));
+  VG_TRY(query_open(ctx, "vg_scan_info"));
   double pose[12];
   if (pose12) {
     memcpy(pose, pose12, sizeof(pose));

@@ -34,7 +34,8 @@
 // k_nav_sum: the summary's counts of the finished field, one atomic per wave and
 // count. k_nav_descend: one lane per start walks down the field, the 8 neighbours'
 // loads of a step issued together.
-#include "vg_internal.h"
+#include "vg_query.h"
+#include "vg_reduce.h"
 
 namespace vg {
 
@@ -49,12 +50,6 @@ static_assert(kNavBlock == 4 * kNavTile && kNavRows == 16, "a thread's run of ce
 
 // the summary's int64 slots as the kernels index them (vg_nav_summary's order)
 enum { kNavUsed = 0, kNavIgnored, kNavPassable, kNavReached, kNavSaturated, kNavMaxPot, kNavRounds, kNavTileRuns };
-
-__device__ __forceinline__ unsigned long long nav_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0's is the wave's)
-}
 
 // p + w, saturating at kNavSat (p <= kNavSat, w < 2^22)
 __device__ __forceinline__ unsigned nav_add(unsigned p, unsigned w) {
@@ -99,9 +94,9 @@ __global__ void __launch_bounds__(kNavBlock) k_nav_init(const uint8_t* __restric
     }
     n_used = used, n_ign = !used;
   }
-  n_pass = nav_wave_sum(n_pass);
-  n_used = nav_wave_sum(n_used);
-  n_ign = nav_wave_sum(n_ign);
+  n_pass = wave_sum(n_pass);
+  n_used = wave_sum(n_used);
+  n_ign = wave_sum(n_ign);
   if ((threadIdx.x & 63) == 0) {
     if (n_pass) atomicAdd(&sum[kNavPassable], n_pass);
     if (n_used) atomicAdd(&sum[kNavUsed], n_used);
@@ -211,13 +206,9 @@ __global__ void __launch_bounds__(kNavBlock) k_nav_sum(const unsigned* __restric
     n_sat += p == kNavSat;
     if (p != kNavUnreached && p > p_max) p_max = p;
   }
-  n_reached = nav_wave_sum(n_reached);
-  n_sat = nav_wave_sum(n_sat);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_down(p_max, off, 64);
-    p_max = o > p_max ? o : p_max;
-  }
+  n_reached = wave_sum(n_reached);
+  n_sat = wave_sum(n_sat);
+  p_max = wave_max(p_max);
   if ((threadIdx.x & 63) == 0) {
     if (n_reached) atomicAdd(&sum[kNavReached], n_reached);
     if (n_sat) atomicAdd(&sum[kNavSaturated], n_sat);
@@ -315,12 +306,12 @@ int navfn_dev(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const 
   VG_TRY(nav_bufs(ctx, cells, tiles));
   hipStream_t s = ctx->stream;
   unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
-  const uint8_t* d_cost = cost ? b.cost.p : ctx->clr.cost.p;
+  const uint8_t* d_cost;
   int* act[2] = {b.act, b.act + tiles};
   b.t.clear();
   VG_HIP(hipMemcpyAsync(b.table, table, 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
   VG_HIP(hipMemcpyAsync(b.goals, goals, 2 * (size_t)n_goals * sizeof(int), hipMemcpyHostToDevice, s));
-  if (cost) VG_HIP(hipMemcpyAsync(b.cost, cost, cells, hipMemcpyHostToDevice, s));
+  VG_TRY(plane_in(ctx, cost, b.cost, ctx->clr.cost.p, cells, &d_cost));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_nav_summary), s));
   VG_HIP(hipMemsetAsync(b.act, 0, 2 * tiles * sizeof(int), s));
   VG_HIP(b.t.begin(s));

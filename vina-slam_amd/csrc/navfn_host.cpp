@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "vg_host.h"
+#include "vg_query.h"
 
 namespace vg {
 
@@ -26,26 +27,14 @@ int host_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const
   uint16_t table[256];
   if (trav) memcpy(table, trav, sizeof(table));
   else if (!nav_table(prm, table)) return VG_E_ARG;
-  if (ctx->shard.world > 1) {
-    ctx->err = "vg_navfn: the context is sharded (world > 1)";
-    return VG_E_STATE;
-  }
-  VG_TRY(host_quiesce(ctx));
-  if (!cost && (!ctx->clr.cost || ctx->clr.nx != prm->nx || ctx->clr.ny != prm->ny)) {
-    ctx->err = ctx->clr.nx ? "vg_navfn: cost == NULL, and the last vg_clearance call's nx, ny differ from prm's"
-                           : "vg_navfn: cost == NULL, and no vg_clearance call left a cost plane on this context";
-    return VG_E_STATE;
-  }
+  VG_TRY(query_open(ctx, "vg_navfn"));
+  if (!cost) VG_TRY(held_cost_ok(ctx, "vg_navfn", "cost == NULL", prm->nx, prm->ny));
   return navfn_dev(ctx, cost, prm, table, goals, n_goals, pot, out);
 }
 
 int host_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len, int32_t* cells, int32_t* len,
                    int32_t* status, int64_t* path_cost) {
-  if (ctx->shard.world > 1) {
-    ctx->err = "vg_nav_paths: the context is sharded (world > 1)";
-    return VG_E_STATE;
-  }
-  VG_TRY(host_quiesce(ctx));
+  VG_TRY(query_open(ctx, "vg_nav_paths"));
   if (!ctx->nav.nx) {
     ctx->err = "vg_nav_paths: no vg_navfn call left a field on this context";
     return VG_E_STATE;
@@ -58,9 +47,7 @@ int host_nav_paths(vg_ctx* ctx, const int32_t* starts, int n_starts, int max_len
 extern "C" int vg_navfn(vg_ctx* ctx, const uint8_t* cost, const vg_nav_params* prm, const uint16_t* trav,
                         const int32_t* goals, int n_goals, uint32_t* pot, vg_nav_summary* out) {
   if (!ctx || !prm || !goals || !out) return VG_E_ARG;
-  if (prm->nx < 1 || prm->ny < 1 || prm->nx > VG_CLR_MAX_SIDE || prm->ny > VG_CLR_MAX_SIDE ||
-      (long long)prm->nx * (long long)prm->ny > (long long)VG_OCC_MAX_CELLS)
-    return VG_E_ARG;
+  if (!vg::grid_shape_ok(prm->nx, prm->ny, VG_CLR_MAX_SIDE)) return VG_E_ARG;
   if (n_goals < 1 || n_goals > VG_NAV_MAX_POINTS) return VG_E_ARG;
   if (prm->flags & ~1) return VG_E_ARG;
   if (prm->neutral < 0 || prm->lethal_from < 0 || prm->lethal_from > 255 || prm->unknown_as < 0 || prm->unknown_as > 254)

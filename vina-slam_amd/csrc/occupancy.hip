@@ -17,17 +17,14 @@
 // Every sum is an integer atomic: the planes, the grid and the summary do not
 // depend on the order of the rays or on how M is cut into launches.
 #include "vg_occ.h"
+#include "vg_query.h"
+#include "vg_reduce.h"
 
 namespace vg {
 
 // the summary's int64 slots as the kernels index them (vg_occ_summary's order)
 enum { kOccRays = 0, kOccHits, kOccInBand, kOccTrunc, kOccOccupied, kOccInvalid, kOccFreeMarks, kOccOccMarks,
        kOccCellsFree, kOccCellsOccupied, kOccCellsUnknown };
-
-__device__ __forceinline__ void occ_wave_add(unsigned long long* __restrict__ sum, int slot, bool mine) {
-  const unsigned long long b = __ballot(mine);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&sum[slot], (unsigned long long)__popcll(b));
-}
 
 __global__ void __launch_bounds__(kOccBlock) k_occ_cast(double vs, DevMap m, const double* __restrict__ pos,
                                                         const double* __restrict__ dirs, int D, int n, OccPrm prm,
@@ -45,11 +42,11 @@ __global__ void __launch_bounds__(kOccBlock) k_occ_cast(double vs, DevMap m, con
     flags = h.flags;
     occ_ray(prm, o, dir, h, n_free, n_occ, in_band);
   }
-  occ_wave_add(sum, kOccHits, valid && (flags & kRayHit));
-  occ_wave_add(sum, kOccInBand, in_band);
-  occ_wave_add(sum, kOccTrunc, valid && (flags & kRayTruncated));
-  occ_wave_add(sum, kOccOccupied, valid && (flags & kRayOccupied));
-  occ_wave_add(sum, kOccInvalid, valid && (flags & kRayInvalid));
+  wave_count_add(sum, kOccHits, valid && (flags & kRayHit));
+  wave_count_add(sum, kOccInBand, in_band);
+  wave_count_add(sum, kOccTrunc, valid && (flags & kRayTruncated));
+  wave_count_add(sum, kOccOccupied, valid && (flags & kRayOccupied));
+  wave_count_add(sum, kOccInvalid, valid && (flags & kRayInvalid));
 }
 
 __global__ void __launch_bounds__(kOccBlock) k_occ_classify(const int* __restrict__ n_free,
@@ -66,16 +63,11 @@ __global__ void __launch_bounds__(kOccBlock) k_occ_classify(const int* __restric
     else cls = f >= min_free ? VG_OCC_FREE : VG_OCC_UNKNOWN;
     grid[i] = (int8_t)cls;
   }
-  occ_wave_add(sum, kOccCellsFree, cls == VG_OCC_FREE);
-  occ_wave_add(sum, kOccCellsOccupied, cls == VG_OCC_OCCUPIED);
-  occ_wave_add(sum, kOccCellsUnknown, cls == VG_OCC_UNKNOWN);
+  wave_count_add(sum, kOccCellsFree, cls == VG_OCC_FREE);
+  wave_count_add(sum, kOccCellsOccupied, cls == VG_OCC_OCCUPIED);
+  wave_count_add(sum, kOccCellsUnknown, cls == VG_OCC_UNKNOWN);
   // the planes' sums, in 64 bits: 64 counts of up to M D each
-  unsigned long long sf = (unsigned long long)f, so = (unsigned long long)o;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sf += __shfl_down(sf, off, 64);
-    so += __shfl_down(so, off, 64);
-  }
+  const unsigned long long sf = wave_sum((unsigned long long)f), so = wave_sum((unsigned long long)o);
   if ((threadIdx.x & 63) == 0) {
     if (sf) atomicAdd(&sum[kOccFreeMarks], sf);
     if (so) atomicAdd(&sum[kOccOccMarks], so);
@@ -106,23 +98,14 @@ int occupancy_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, con
   unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(b.sum.p);
   int* d_free = b.planes;
   int* d_occ = b.planes + cells;
-  const int slab = kInfoSlab;  // (slab D <= 2^24 lanes per launch)
   b.t.clear();
   VG_HIP(hipMemsetAsync(b.planes, 0, 2 * cells * sizeof(int), s));
   VG_HIP(hipMemsetAsync(d_sum, 0, sizeof(vg_occ_summary), s));
   if (M > 0) VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-  for (int i0 = 0; i0 < M; i0 += slab) {
-    const int m = M - i0 < slab ? M - i0 : slab;
-    const int n = m * D;
-    VG_HIP(hipMemcpyAsync(b.pos, positions + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    VG_HIP(b.t.begin(s));
+  VG_TRY(ray_slabs(ctx, positions, M, D, b.t, [&](int m, int n) {
     k_occ_cast<<<(n + kOccBlock - 1) / kOccBlock, kOccBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, n, q, d_free,
                                                                      d_occ, d_sum);
-    VG_HIP(b.t.end(s));
-    VG_HIP(hipGetLastError());
-    VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
-    VG_HIP(b.t.collect());
-  }
+  }));
   VG_HIP(b.t.begin(s));
   k_occ_classify<<<(int)((cells + kOccBlock - 1) / kOccBlock), kOccBlock, 0, s>>>(d_free, d_occ, (int)cells, q.min_occ,
                                                                                   q.min_free, q.occ_ratio, b.grid, d_sum);

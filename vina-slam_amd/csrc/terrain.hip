@@ -27,6 +27,8 @@
 //
 // Every sum is an integer atomic, min and max commute: no output depends on the
 // order of the rays or on how M is cut into launches.
+#include "vg_query.h"
+#include "vg_reduce.h"
 #include "vg_terrain.h"
 
 namespace vg {
@@ -38,11 +40,6 @@ enum { kTerRays = 0, kTerHits, kTerInBand, kTerTrunc, kTerOccupied, kTerInvalid,
 constexpr int kTerTileX = 32, kTerTileY = 8;  // kTerTileX kTerTileY = kOccBlock
 static_assert(kTerTileX * kTerTileY == kOccBlock, "one lane per cell of the tile");
 constexpr int kTerClassifyBlocks = 2048;  // k_ter_classify's launch at most: 8 workgroups per CU, each striding over the cells
-
-__device__ __forceinline__ void ter_wave_add(unsigned long long* __restrict__ sum, int slot, bool mine) {
-  const unsigned long long b = __ballot(mine);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&sum[slot], (unsigned long long)__popcll(b));
-}
 
 __global__ void __launch_bounds__(kOccBlock) k_ter_ground(double vs, DevMap m, const double* __restrict__ pos,
                                                           const double* __restrict__ dirs, int D, int n, TerPrm prm,
@@ -61,12 +58,12 @@ __global__ void __launch_bounds__(kOccBlock) k_ter_ground(double vs, DevMap m, c
     flags = h.flags;
     ter_ground(prm, o, dir, h, g_n, g_sum, g_min, g_max, ground, oor);
   }
-  ter_wave_add(sum, kTerHits, valid && (flags & kRayHit));
-  ter_wave_add(sum, kTerTrunc, valid && (flags & kRayTruncated));
-  ter_wave_add(sum, kTerOccupied, valid && (flags & kRayOccupied));
-  ter_wave_add(sum, kTerInvalid, valid && (flags & kRayInvalid));
-  ter_wave_add(sum, kTerGround, ground);
-  ter_wave_add(sum, kTerOutOfRange, oor);
+  wave_count_add(sum, kTerHits, valid && (flags & kRayHit));
+  wave_count_add(sum, kTerTrunc, valid && (flags & kRayTruncated));
+  wave_count_add(sum, kTerOccupied, valid && (flags & kRayOccupied));
+  wave_count_add(sum, kTerInvalid, valid && (flags & kRayInvalid));
+  wave_count_add(sum, kTerGround, ground);
+  wave_count_add(sum, kTerOutOfRange, oor);
 }
 
 // floor(s / n) where n >= min_ground (>= 1), else none
@@ -113,14 +110,9 @@ __global__ void __launch_bounds__(kOccBlock) k_ter_cells(const int* __restrict__
     step[c] = st;
   }
   // the three reductions: wave, LDS across the waves, one global atomic each
-  int cnt = has;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64);
-    const int a = __shfl_down(st, off, 64), b = __shfl_down(spread, off, 64);
-    st = a > st ? a : st;
-    spread = b > spread ? b : spread;
-  }
+  const int cnt = wave_sum(has);
+  st = wave_max(st);
+  spread = wave_max(spread);
   if ((threadIdx.x & 63) == 0) {
     if (cnt) atomicAdd(&red[0], cnt);
     if (st) atomicMax(&red[1], st);
@@ -148,7 +140,7 @@ __global__ void __launch_bounds__(kOccBlock) k_ter_marks(double vs, DevMap m, co
     ray_trace(m, vs, o, dir, prm.ray, h);
     ter_marks(prm, o, dir, h, elev, n_free, n_occ, in_band);
   }
-  ter_wave_add(sum, kTerInBand, in_band);
+  wave_count_add(sum, kTerInBand, in_band);
 }
 
 __global__ void __launch_bounds__(kOccBlock) k_ter_classify(const int* __restrict__ n_free,
@@ -183,8 +175,7 @@ __global__ void __launch_bounds__(kOccBlock) k_ter_classify(const int* __restric
   // workgroup's add, so the launch is held to kTerClassifyBlocks workgroups that stride over the cells
 #pragma unroll
   for (int k = 0; k < kSums; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_down(a[k], off, 64);
+    a[k] = wave_sum(a[k]);
     if ((threadIdx.x & 63) == 0 && a[k]) atomicAdd(&red[k], a[k]);
   }
   __syncthreads();
@@ -241,7 +232,6 @@ int terrain_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const
   const TerPrm q = ter_prm(prm);
   int* d_free = b.planes;
   int* d_occ = b.planes + cells;
-  const int slab = kInfoSlab;  // (slab D <= 2^24 lanes per launch)
   for (KernelTimer& k : t.t) k.clear();
   VG_HIP(hipMemsetAsync(b.planes, 0, 2 * cells * sizeof(int), s));
   VG_HIP(hipMemsetAsync(t.gn, 0, cells * sizeof(int), s));
@@ -251,23 +241,14 @@ int terrain_dev(vg_ctx* ctx, const MP& mp, const double* positions, int M, const
   VG_HIP(hipMemsetAsync(t.sum, 0, kTerSlots * sizeof(unsigned long long), s));
   if (M > 0) VG_HIP(hipMemcpyAsync(b.dirs, dirs, (size_t)D * 3 * sizeof(double), hipMemcpyHostToDevice, s));
   for (int pass = 0; pass < 2; pass++) {
-    KernelTimer& kt = t.t[pass ? 2 : 0];
-    for (int i0 = 0; i0 < M; i0 += slab) {
-      const int m = M - i0 < slab ? M - i0 : slab;
-      const int n = m * D;
-      VG_HIP(hipMemcpyAsync(b.pos, positions + 3 * (size_t)i0, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-      VG_HIP(kt.begin(s));
+    VG_TRY(ray_slabs(ctx, positions, M, D, t.t[pass ? 2 : 0], [&](int m, int n) {
       if (pass == 0)
         k_ter_ground<<<(n + kOccBlock - 1) / kOccBlock, kOccBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, n, q, t.gn,
                                                                            t.gsum, t.gmin, t.gmax, t.sum);
       else
         k_ter_marks<<<(n + kOccBlock - 1) / kOccBlock, kOccBlock, 0, s>>>(mp.vs, ctx->map, b.pos, b.dirs, D, n, q, t.elev,
                                                                           d_free, d_occ, t.sum);
-      VG_HIP(kt.end(s));
-      VG_HIP(hipGetLastError());
-      VG_HIP(hipStreamSynchronize(s));  // the slab's staging is reused by the next
-      VG_HIP(kt.collect());
-    }
+    }));
     if (pass == 0) VG_TRY(ter_cells_launch(ctx, q.nx, q.ny, q.min_ground));
   }
   VG_HIP(t.t[3].begin(s));
@@ -330,9 +311,7 @@ extern "C" int vgx_ter_ground(vg_ctx* ctx, int nx, int ny, int32_t* g_n, int64_t
 }
 extern "C" int vgx_ter_cells(vg_ctx* ctx, int nx, int ny, int min_ground, const int32_t* g_n, const int64_t* g_sum,
                              const int32_t* g_min, const int32_t* g_max, int32_t* elev, int32_t* step, int64_t* out3) {
-  if (!ctx || !g_n || !g_sum || !g_min || !g_max || !out3 || nx < 1 || ny < 1 ||
-      (long long)nx * (long long)ny > (long long)VG_OCC_MAX_CELLS)
-    return VG_E_ARG;
+  if (!ctx || !g_n || !g_sum || !g_min || !g_max || !out3 || !vg::grid_shape_ok(nx, ny, 0)) return VG_E_ARG;
   const size_t cells = (size_t)nx * (size_t)ny;
   VG_TRY(vg::ter_bufs(ctx, cells, false));
   vg::TerBufs& t = ctx->ter;

@@ -4,16 +4,13 @@
 #include <cmath>
 
 #include "vg_host.h"
+#include "vg_query.h"
 
 namespace vg {
 
 int host_terrain(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D, const vg_terrain_params* prm,
                  int8_t* grid, int32_t* elev, int32_t* step, int32_t* counts, vg_terrain_summary* out) {
-  if (ctx->shard.world > 1) {
-    ctx->err = "vg_terrain: the context is sharded (world > 1)";
-    return VG_E_STATE;
-  }
-  VG_TRY(host_quiesce(ctx));
+  VG_TRY(query_open(ctx, "vg_terrain"));
   return terrain_dev(ctx, hp(ctx)->mpd, positions, M, dirs, D, prm, grid, elev, step, counts, out);
 }
 
@@ -25,12 +22,7 @@ static bool ter_pair_ok(double lo, double hi) { return (lo == 0.0 && hi == 0.0) 
 extern "C" int vg_terrain(vg_ctx* ctx, const double* positions, int M, const double* dirs, int D,
                           const vg_terrain_params* prm, int8_t* grid, int32_t* elev, int32_t* step, int32_t* counts,
                           vg_terrain_summary* out) {
-  if (!ctx || !prm || !grid || !out || !dirs || M < 0 || (M > 0 && !positions)) return VG_E_ARG;
-  if (D < 1 || D > vg::kInfoMaxDirs) return VG_E_ARG;
-  if (!(prm->res > 0.0) || !std::isfinite(prm->res) || !std::isfinite(prm->x0) || !std::isfinite(prm->y0))
-    return VG_E_ARG;
-  if (prm->nx < 1 || prm->ny < 1 || (long long)prm->nx * (long long)prm->ny > (long long)VG_OCC_MAX_CELLS)
-    return VG_E_ARG;
+  if (!vg::ray_grid_args_ok(ctx, positions, M, dirs, D, prm, grid, out)) return VG_E_ARG;
   if (prm->flags & ~3) return VG_E_ARG;
   if (!std::isfinite(prm->z_res) || !std::isfinite(prm->up_min)) return VG_E_ARG;
   if (!vg::ter_pair_ok(prm->g_lo, prm->g_hi) || !vg::ter_pair_ok(prm->clear_lo, prm->clear_hi)) return VG_E_ARG;

@@ -1,8 +1,9 @@
 // vg_scratch.h — the two owning types behind the query-side scratch (score,
-// raycast, localisability, occupancy, clearance, navfn, the change layer, the
-// place index, markers, the fleet's tables and the transient device scratch of
-// checkpoint / lifetime / la_probe). Self-contained: the HIP runtime API and
-// the standard library, nothing of the context.
+// raycast, localisability, occupancy, terrain, clearance, navfn, frontiers, view
+// gain, the change layer, the place index, markers, the fleet's tables and the
+// transient device scratch of checkpoint / lifetime / la_probe). Self-contained:
+// the HIP runtime API and the standard library, nothing of the context; what the
+// query layers share on top of them is vg_query.h and vg_reduce.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstddef>

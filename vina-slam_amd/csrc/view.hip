@@ -35,7 +35,8 @@
 // maxima only: nothing depends on the order in which workgroups arrive.
 #include <cstddef>
 
-#include "vg_internal.h"
+#include "vg_query.h"
+#include "vg_reduce.h"
 
 namespace vg {
 
@@ -56,16 +57,6 @@ __device__ __forceinline__ int view_class(int8_t v) {
 }
 __device__ __forceinline__ int view_staged(const unsigned* s_cls, int idx) {
   return (s_cls[idx >> 4] >> ((idx & 15) * 2)) & 3;
-}
-__device__ __forceinline__ int view_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // (lane 0's is the wave's)
-}
-__device__ __forceinline__ u64 view_wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 // grid: n_views workgroups; dynamic LDS: n_bm words, with kStage another ceil(W^2 / 16)
@@ -169,8 +160,8 @@ __global__ void __launch_bounds__(kViewBlock) k_view_rays(const int8_t* __restri
       atomicAdd(&seen[g], 1);
     }
   }
-  n_unk = view_wave_sum(n_unk), n_free = view_wave_sum(n_free), n_occ = view_wave_sum(n_occ);
-  n_open = view_wave_sum(n_open);
+  n_unk = wave_sum(n_unk), n_free = wave_sum(n_free), n_occ = wave_sum(n_occ);
+  n_open = wave_sum(n_open);
   if ((tid & 63) == 0) {
     int* r = s_red[tid >> 6];
     r[0] = n_unk, r[1] = n_free, r[2] = n_occ, r[3] = n_open;
@@ -183,20 +174,6 @@ __global__ void __launch_bounds__(kViewBlock) k_view_rays(const int8_t* __restri
     }
     rec.n_visible = rec.n_unknown + rec.n_free + rec.n_occupied;
     recs[blockIdx.x] = rec;
-  }
-}
-
-// the workgroup's sum of v to sum[slot] (one atomic, none for a zero); every lane calls it
-__device__ __forceinline__ void view_block_add(u64 v, u64* sum, int slot) {
-  __shared__ u64 s_w[kViewWaves];
-  v = view_wave_sum(v);
-  __syncthreads();  // (a call before this one has read s_w)
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 t = 0;
-    for (int w = 0; w < kViewWaves; w++) t += s_w[w];
-    if (t) atomicAdd(&sum[slot], t);
   }
 }
 
@@ -217,17 +194,13 @@ __global__ void __launch_bounds__(kViewBlock) k_view_sum(const int8_t* __restric
       key = k > key ? k : key;
     }
   }
-  view_block_add(n_seen, sum, kVwCells);
-  view_block_add(n_unk, sum, kVwUnknown);
-  view_block_add(n_ok, sum, kVwOk);
-  view_block_add(n_ok * (u64)(8 * R), sum, kVwRays);
-  view_block_add(n_out, sum, kVwOutside);
-  view_block_add(n_blk, sum, kVwBlocked);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 o = __shfl_down(key, off, 64);
-    key = o > key ? o : key;
-  }
+  block_add<kViewBlock>(n_seen, sum, kVwCells);
+  block_add<kViewBlock>(n_unk, sum, kVwUnknown);
+  block_add<kViewBlock>(n_ok, sum, kVwOk);
+  block_add<kViewBlock>(n_ok * (u64)(8 * R), sum, kVwRays);
+  block_add<kViewBlock>(n_out, sum, kVwOutside);
+  block_add<kViewBlock>(n_blk, sum, kVwBlocked);
+  key = wave_max(key);
   if ((threadIdx.x & 63) == 0 && key) atomicMax(&sum[kVwKey], key);
 }
 
@@ -246,14 +219,14 @@ int view_gain_dev(vg_ctx* ctx, const int8_t* grid, const vg_view_params* prm, co
   VG_HIP(b.seen.reserve(cells));
   if (grid) VG_HIP(b.grid.reserve(cells));
   hipStream_t s = ctx->stream;
-  const int8_t* d_grid = grid ? b.grid.p : ctx->occ.grid.p;
+  const int8_t* d_grid;
   const bool stage = b.stage && (size_t)(n_bm + n_cls) * sizeof(unsigned) <= kViewLdsMax;
   const size_t lds = (size_t)(n_bm + (stage ? n_cls : 0)) * sizeof(unsigned);
   static_assert((size_t)((2 * VG_VIEW_MAX_RADIUS + 1) * (2 * VG_VIEW_MAX_RADIUS + 1) + 31) / 32 * sizeof(unsigned) <=
                     kViewLdsMax, "the bitmap of the largest radius fits the LDS of a workgroup");
   u64 h_sum[kVwSlots];
   b.t.clear();
-  if (grid) VG_HIP(hipMemcpyAsync(b.grid, grid, cells, hipMemcpyHostToDevice, s));
+  VG_TRY(plane_in(ctx, grid, b.grid, ctx->occ.grid.p, cells, &d_grid));
   VG_HIP(hipMemcpyAsync(b.views, views, 2 * (size_t)n_views * sizeof(int), hipMemcpyHostToDevice, s));
   VG_HIP(b.t.begin(s));
   VG_HIP(hipMemsetAsync(b.sum, 0, kVwSlots * sizeof(u64), s));

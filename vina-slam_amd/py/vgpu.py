@@ -858,6 +858,29 @@ class VgError(RuntimeError):
     pass
 
 
+def _plane_arg(who, name, arr, dtype, nx, ny):
+    """A 2-D query's plane argument: (arr as a contiguous dtype [ny, nx] array, or None: the plane a call before left
+    on the device; nx; ny). An array brings its shape, which nx and ny may repeat; None needs both."""
+    if arr is None:
+        if nx is None or ny is None:
+            raise ValueError("%s: %s=None needs nx and ny" % (who, name))
+        return None, nx, ny
+    a = np.ascontiguousarray(arr, dtype=dtype)
+    if a.ndim != 2 or (nx not in (None, a.shape[1])) or (ny not in (None, a.shape[0])):
+        raise ValueError("%s: %s is [ny, nx]" % (who, name))
+    return a, a.shape[1], a.shape[0]
+
+
+def _grid_legal(nx, ny):
+    """The library's shape check of the 2-D query layers: outputs are sized by nx, ny only where it passes."""
+    return 1 <= nx <= CLR_MAX_SIDE and 1 <= ny <= CLR_MAX_SIDE and nx * ny <= OCC_MAX_CELLS
+
+
+def _summary(s):
+    """A summary structure as a dict of ints, without its reserved field."""
+    return {f: int(getattr(s, f)) for f, _ in s._fields_ if f != "reserved"}
+
+
 class Context:
     """One device-resident LIO sequence (vg_ctx)."""
 
@@ -873,6 +896,12 @@ class Context:
     def _chk(self, r, what):
         if r != 0:
             raise VgError("%s failed (%d): %s" % (what, r, lib().vg_last_error(self.h).decode()))
+
+    def _ms(self, fn, name):
+        """A measurement hook's one value: fn(ctx, double*) named `name`."""
+        ms = ctypes.c_double(0)
+        self._chk(fn(self.h, ctypes.byref(ms)), name)
+        return ms.value
 
     def close(self):
         """vg_destroy; refused (VgError -5, the context stays) while contexts are attached to
@@ -1068,9 +1097,7 @@ class Context:
 
     def score_ms(self):
         """Device time of the last score_poses call's kernels (HIP events on the context stream), ms."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_score_ms(self.h, ctypes.byref(ms)), "vgx_score_ms")
-        return ms.value
+        return self._ms(lib().vgx_score_ms, "vgx_score_ms")
 
     def relocalize(self, xyz, guess, install=False, **params):
         """vg_relocalize: (pose (12,), the refined winner's record, ok). guess: (12,) [R, p]; params: reloc_params."""
@@ -1144,9 +1171,7 @@ class Context:
     def info_ms(self):
         """Device time (ms) of the last localizability call's kernels, summed over its slabs, or of the
         last scan_info call's (HIP events on the context stream)."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_info_ms(self.h, ctypes.byref(ms)), "vgx_info_ms")
-        return ms.value
+        return self._ms(lib().vgx_info_ms, "vgx_info_ms")
 
     def info_slab(self, places):
         """Test hook: the places per launch of localizability from the next call on (<= 0: the default)."""
@@ -1170,14 +1195,11 @@ class Context:
         self._chk(lib().vg_occupancy(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0],
                                      _d(d) if d.shape[0] else None, d.shape[0], ctypes.byref(p), grid.ctypes.data,
                                      None if cnt is None else cnt.ctypes.data, ctypes.byref(s)), "vg_occupancy")
-        summ = {f: int(getattr(s, f)) for f, _ in OccSummary._fields_ if f != "reserved"}
-        return grid.reshape(p.ny, p.nx), None if cnt is None else cnt.reshape(2, p.ny, p.nx), summ
+        return grid.reshape(p.ny, p.nx), None if cnt is None else cnt.reshape(2, p.ny, p.nx), _summary(s)
 
     def occ_ms(self):
         """Device time (ms) of the last occupancy call's kernels, summed over its slabs and the classification."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_occ_ms(self.h, ctypes.byref(ms)), "vgx_occ_ms")
-        return ms.value
+        return self._ms(lib().vgx_occ_ms, "vgx_occ_ms")
 
     # ---- the terrain layer (vina_gpu.h "Terrain layer")
     def terrain(self, positions, dirs=None, **params):
@@ -1199,9 +1221,8 @@ class Context:
         self._chk(lib().vg_terrain(self.h, _d(pos) if pos.shape[0] else None, pos.shape[0],
                                    _d(d) if d.shape[0] else None, d.shape[0], ctypes.byref(p), grid.ctypes.data,
                                    elev.ctypes.data, step.ctypes.data, cnt.ctypes.data, ctypes.byref(s)), "vg_terrain")
-        summ = {f: int(getattr(s, f)) for f, _ in TerrainSummary._fields_}
         return (grid.reshape(p.ny, p.nx), elev.reshape(p.ny, p.nx), step.reshape(p.ny, p.nx),
-                cnt.reshape(2, p.ny, p.nx), summ)
+                cnt.reshape(2, p.ny, p.nx), _summary(s))
 
     def terrain_ground(self, nx, ny):
         """Test hook (vgx_ter_ground): the four ground planes the last terrain() call left on the device, (g_n
@@ -1242,21 +1263,14 @@ class Context:
         (uint8, COST_*) leave the device. Returns ({name: array [ny, nx]}, the summary as a dict)."""
         if not lib().has_clearance:
             raise VgError("this libvina_gpu.so has no clearance field (vg_clearance): rebuild it")
-        g = None
-        if grid is not None:
-            g = np.ascontiguousarray(grid, dtype=np.int8)
-            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
-                raise ValueError("clearance: grid is [ny, nx]")
-            ny, nx = g.shape
-        elif nx is None or ny is None:
-            raise ValueError("clearance: grid=None needs nx and ny")
+        g, nx, ny = _plane_arg("clearance", "grid", grid, np.int8, nx, ny)
         unknown = [w for w in want if w not in ("dist2", "nearest", "cost")]
         if unknown:
             raise ValueError("clearance: want holds %r" % unknown)
         p = ClrParams()
         p.nx, p.ny, p.res, p.flags = int(nx), int(ny), res, flags
         p.inscribed_radius, p.inflation_radius, p.cost_scaling = inscribed_radius, inflation_radius, cost_scaling
-        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        legal = _grid_legal(p.nx, p.ny)
         shape = (p.ny, p.nx) if legal else (1, 1)
         out = {w: np.zeros(shape, dtype=np.uint8 if w == "cost" else np.int32) for w in ("dist2", "nearest", "cost")
                if w in want}
@@ -1264,13 +1278,11 @@ class Context:
         self._chk(lib().vg_clearance(self.h, None if g is None else g.ctypes.data, ctypes.byref(p),
                                      *[out[w].ctypes.data if w in out else None for w in ("dist2", "nearest", "cost")],
                                      ctypes.byref(s)), "vg_clearance")
-        return out, {f: int(getattr(s, f)) for f, _ in ClrSummary._fields_ if f != "reserved"}
+        return out, _summary(s)
 
     def clearance_ms(self):
         """Device time (ms) of the last clearance call's two kernels."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_clr_ms(self.h, ctypes.byref(ms)), "vgx_clr_ms")
-        return ms.value
+        return self._ms(lib().vgx_clr_ms, "vgx_clr_ms")
 
     # ---- the navigation function (vina_gpu.h "Navigation function")
     def navfn(self, cost=None, goals=(), *, nx=None, ny=None, want_pot=True, trav=None, **params):
@@ -1282,14 +1294,7 @@ class Context:
         nav_paths()."""
         if not lib().has_navfn:
             raise VgError("this libvina_gpu.so has no navigation function (vg_navfn): rebuild it")
-        c = None
-        if cost is not None:
-            c = np.ascontiguousarray(cost, dtype=np.uint8)
-            if c.ndim != 2 or (nx not in (None, c.shape[1])) or (ny not in (None, c.shape[0])):
-                raise ValueError("navfn: cost is [ny, nx]")
-            ny, nx = c.shape
-        elif nx is None or ny is None:
-            raise ValueError("navfn: cost=None needs nx and ny")
+        c, nx, ny = _plane_arg("navfn", "cost", cost, np.uint8, nx, ny)
         g = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 2)
         t = None
         if trav is not None:
@@ -1302,13 +1307,13 @@ class Context:
             if k not in ("flags", "neutral", "lethal_from", "unknown_as", "factor"):
                 raise ValueError("navfn: no parameter %r" % k)
             setattr(p, k, v)
-        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        legal = _grid_legal(p.nx, p.ny)
         pot = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.uint32) if want_pot else None
         s = NavSummary()
         self._chk(lib().vg_navfn(self.h, None if c is None else c.ctypes.data, ctypes.byref(p),
                                  None if t is None else t.ctypes.data, g.ctypes.data, g.shape[0],
                                  None if pot is None else pot.ctypes.data, ctypes.byref(s)), "vg_navfn")
-        return pot, {f: int(getattr(s, f)) for f, _ in NavSummary._fields_ if f != "reserved"}
+        return pot, _summary(s)
 
     def nav_paths(self, starts, max_len):
         """vg_nav_paths from starts ((S, 2) cells ix, iy) down the field of the last navfn() call. Returns
@@ -1328,9 +1333,7 @@ class Context:
 
     def navfn_ms(self):
         """Device time (ms) of the last navfn() or nav_paths() call's kernels."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_nav_ms(self.h, ctypes.byref(ms)), "vgx_nav_ms")
-        return ms.value
+        return self._ms(lib().vgx_nav_ms, "vgx_nav_ms")
 
     # ---- exploration frontiers (vina_gpu.h "Exploration frontiers")
     def frontiers(self, grid=None, *, nx=None, ny=None, cost=None, use_cost=False, use_pot=False, cost_max=0,
@@ -1344,14 +1347,8 @@ class Context:
         max_records; the summary as a dict)."""
         if not lib().has_frontiers:
             raise VgError("this libvina_gpu.so has no exploration frontiers (vg_frontiers): rebuild it")
-        g = c = None
-        if grid is not None:
-            g = np.ascontiguousarray(grid, dtype=np.int8)
-            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
-                raise ValueError("frontiers: grid is [ny, nx]")
-            ny, nx = g.shape
-        elif nx is None or ny is None:
-            raise ValueError("frontiers: grid=None needs nx and ny")
+        g, nx, ny = _plane_arg("frontiers", "grid", grid, np.int8, nx, ny)
+        c = None
         if cost is not None:
             c = np.ascontiguousarray(cost, dtype=np.uint8)
             if c.shape != (ny, nx):
@@ -1360,7 +1357,7 @@ class Context:
         p = FrontierParams()
         p.nx, p.ny, p.flags = int(nx), int(ny), (1 if use_cost else 0) | (2 if use_pot else 0)
         p.cost_max, p.min_size = cost_max, min_size
-        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        legal = _grid_legal(p.nx, p.ny)
         labels = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.int32) if want_labels else None
         m = int(max_records)
         recs = np.zeros(min(max(m, 0), FRONTIER_MAX_RECORDS), dtype=FRONTIER_REC)
@@ -1368,13 +1365,11 @@ class Context:
         self._chk(lib().vg_frontiers(self.h, None if g is None else g.ctypes.data, None if c is None else c.ctypes.data,
                                      ctypes.byref(p), None if labels is None else labels.ctypes.data,
                                      recs.ctypes.data if recs.size else None, m, ctypes.byref(s)), "vg_frontiers")
-        return labels, recs[:s.n_written], {f: int(getattr(s, f)) for f, _ in FrontierSummary._fields_ if f != "reserved"}
+        return labels, recs[:s.n_written], _summary(s)
 
     def frontiers_ms(self):
         """Device time (ms) of the last frontiers() call's kernels."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_frontier_ms(self.h, ctypes.byref(ms)), "vgx_frontier_ms")
-        return ms.value
+        return self._ms(lib().vgx_frontier_ms, "vgx_frontier_ms")
 
     # ---- view gain (vina_gpu.h "View gain")
     def view_gain(self, views, radius, grid=None, *, nx=None, ny=None, max_unknown=0, want_seen=False):
@@ -1385,31 +1380,22 @@ class Context:
         OK viewpoints that see each cell, or None without want_seen; the summary as a dict)."""
         if not lib().has_view_gain:
             raise VgError("this libvina_gpu.so has no view gain (vg_view_gain): rebuild it")
-        g = None
-        if grid is not None:
-            g = np.ascontiguousarray(grid, dtype=np.int8)
-            if g.ndim != 2 or (nx not in (None, g.shape[1])) or (ny not in (None, g.shape[0])):
-                raise ValueError("view_gain: grid is [ny, nx]")
-            ny, nx = g.shape
-        elif nx is None or ny is None:
-            raise ValueError("view_gain: grid=None needs nx and ny")
+        g, nx, ny = _plane_arg("view_gain", "grid", grid, np.int8, nx, ny)
         v = np.ascontiguousarray(views, dtype=np.int32).reshape(-1, 2)
         p = ViewParams()
         p.nx, p.ny, p.radius, p.max_unknown = int(nx), int(ny), int(radius), int(max_unknown)
-        legal = 1 <= p.nx <= CLR_MAX_SIDE and 1 <= p.ny <= CLR_MAX_SIDE and p.nx * p.ny <= OCC_MAX_CELLS
+        legal = _grid_legal(p.nx, p.ny)
         seen = np.zeros((p.ny, p.nx) if legal else (1, 1), dtype=np.int32) if want_seen else None
         recs = np.zeros(max(v.shape[0], 1), dtype=VIEW_REC)
         s = ViewSummary()
         self._chk(lib().vg_view_gain(self.h, None if g is None else g.ctypes.data, ctypes.byref(p), v.ctypes.data,
                                      v.shape[0], recs.ctypes.data, None if seen is None else seen.ctypes.data,
                                      ctypes.byref(s)), "vg_view_gain")
-        return recs[:v.shape[0]], seen, {f: int(getattr(s, f)) for f, _ in ViewSummary._fields_ if f != "reserved"}
+        return recs[:v.shape[0]], seen, _summary(s)
 
     def view_gain_ms(self):
         """Device time (ms) of the last view_gain() call's kernels."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_view_ms(self.h, ctypes.byref(ms)), "vgx_view_ms")
-        return ms.value
+        return self._ms(lib().vgx_view_ms, "vgx_view_ms")
 
     # ---- the change layer (vina_gpu.h "Change layer")
     def change_begin(self, cell=0.0, cell_hash_log2=0, **diff):
@@ -1575,9 +1561,7 @@ class Context:
 
     def ray_ms(self):
         """Device time of the last raycast slab's / scan_diff call's kernels (HIP events on the context stream), ms."""
-        ms = ctypes.c_double(0)
-        self._chk(lib().vgx_ray_ms(self.h, ctypes.byref(ms)), "vgx_ray_ms")
-        return ms.value
+        return self._ms(lib().vgx_ray_ms, "vgx_ray_ms")
 
     def _need_checkpoint(self):
         if not lib().has_checkpoint:
