@@ -1176,6 +1176,136 @@ int vg_change_report(vg_ctx* ctx, const vg_change_query* q, vg_change_leaf* leav
 int vg_change_clear(vg_ctx* ctx);
 int vg_change_end(vg_ctx* ctx);
 
+/* ---- Live obstacle layer: what the sensor sees now, folded into the 2-D grid -------
+ * vg_occupancy and vg_terrain give the grid of the saved map. A robot that localises
+ * in it plans through a pallet or a person in the aisle unless what it sees now
+ * reaches that grid. The layer is nav2's obstacle layer in integers: mark where
+ * live returns fall, clear where live beams pass, forget after a while, and hand
+ * vg_clearance and everything behind it one grid.
+ *
+ * State. A layer belongs to the context it was begun on. It holds its geometry
+ * (x0, y0, res, nx, ny with vg_occ_params' meaning; nx ny <= VG_OCC_MAX_CELLS, each
+ * side <= VG_CLR_MAX_SIDE), a private copy of a base grid (int8, VG_OCC_*), two
+ * int32 planes hit and clear, and int64 totals. hit[i] is the largest stamp of a
+ * scan that marked cell i, clear[i] the largest stamp of a scan whose beam crossed
+ * it; 0: never.
+ *
+ * Per point of a marked scan. The point is classified exactly as vg_scan_diff
+ * does: the same class bits, the same o, w and r. cell(v) = (floor((v_x - x0) /
+ * res), floor((v_y - y0) / res)) in double, each index held to [-2^30, 2^30]. With
+ * dz = w_z - o_z, and for a point whose o and w are finite (any other point marks
+ * and clears nothing, and its record's flags and cells are 0):
+ *   In band: z_lo <= dz <= z_hi.
+ *   Obstacle point: the class is VG_DIFF_APPEARED (with params flags bit 0
+ *     VG_DIFF_UNKNOWN too), the point is in band and r_min <= r <= mark_max. It sets
+ *     hit[cell(w)] = max(hit[cell(w)], stamp).
+ *   Clearing beam: every point with r > 0, whatever its class. t_b = r; where
+ *     clear_max < t_b, t_b = clear_max (the beam is cut); then with t_z = z_hi r / dz
+ *     for dz > 0 and z_lo r / dz for dz < 0, where t_z < t_b, t_b = t_z (the beam
+ *     left the band; z_lo <= 0 <= z_hi, so it starts inside). e = o + (t_b / r)(w -
+ *     o), a = cell(o), b = cell(e), n = max(|b_x - a_x|, |b_y - a_y|), s the signs of
+ *     b - a. The beam's cells are the view gain's ray cells from a towards b,
+ *       c_k = (a_x + s_x ((2 k |b_x - a_x| + n) div 2n), a_y + s_y ((2 k |b_y - a_y| + n) div 2n)),
+ *     and cells k = 0 .. n - 1 get clear = max(clear, stamp): the end cell b is never
+ *     cleared by its own beam, and a beam with a == b clears nothing. n <= 4097.
+ *   Marks and clears outside the grid are dropped.
+ * Stamp. Every vg_live_mark call carries an int32 stamp > 0, or 0 for the layer's
+ * largest stamp so far + 1. Both planes are written by integer atomic maxima only:
+ * the layer after a set of (scan, pose, stamp) triples has the same bytes in
+ * whatever order, and at whatever position in its cloud, the points arrived.
+ *
+ * Live cell at time `now`: hit > 0 && hit >= clear && (persist == 0 || now - hit <
+ * persist). A scan that both marks and crosses a cell leaves it occupied (nav2
+ * marks after it clears).
+ * Compose. out[i] = VG_OCC_OCCUPIED where cell i is live, else base[i]; with compose
+ * flags bit 0 a cell that is not live and whose base is VG_OCC_UNKNOWN becomes
+ * VG_OCC_FREE when clear > 0, clear > hit and (persist == 0 || now - clear <
+ * persist). The composed grid is written where vg_occupancy / vg_terrain leave
+ * theirs, with its shape, so that vg_clearance, vg_frontiers and vg_view_gain with
+ * grid == NULL read it unchanged. The layer's base copy is never written: a second
+ * compose does not compound, and a later vg_occupancy does not reach the base. */
+typedef struct vg_live_params {    /* 224 bytes, no implicit padding */
+  vg_diff_params diff;      /* zero fields: vg_scan_diff's defaults */
+  double x0, y0, res;       /* as vg_occ_params */
+  int    nx, ny;
+  double z_lo, z_hi;        /* the band of dz; both 0: -1, 1. z_lo <= 0 <= z_hi, z_lo < z_hi */
+  double r_min;             /* <= 0: 0 */
+  double mark_max;          /* <= 0: no limit */
+  double clear_max;         /* <= 0: 4096 res, or mark_max where that is set and smaller; clear_max / res <= 4096 */
+  int    persist;           /* stamps a mark or a clearing lives; <= 0: 0, for ever */
+  int    flags;             /* bit 0: VG_DIFF_UNKNOWN points mark too */
+  double reserved[4];
+} vg_live_params;
+#define VG_LIVE_MARKS     1   /* vg_live_point.flags: an obstacle point */
+#define VG_LIVE_CLEARS    2   /* a clearing beam */
+#define VG_LIVE_IN_BAND   4   /* z_lo <= dz <= z_hi */
+#define VG_LIVE_CUT       8   /* t_b = clear_max */
+#define VG_LIVE_LEFT_BAND 16  /* t_b = t_z */
+typedef struct vg_live_point {     /* 32 bytes, no implicit padding */
+  int32_t cls;                     /* VG_DIFF_* */
+  int32_t flags;                   /* VG_LIVE_* */
+  int32_t ax, ay, bx, by;          /* cell(o), cell(e); 0 without a clearing beam */
+  int32_t mx, my;                  /* cell(w) */
+} vg_live_point;
+typedef struct vg_live_summary {   /* 128 bytes, int64 only, no implicit padding */
+  int64_t n[4];                    /* points per class, indexed by VG_DIFF_* */
+  int64_t n_obstacle;              /* obstacle points */
+  int64_t marks_dropped;           /* ... whose cell lies outside the grid */
+  int64_t n_beams;                 /* clearing beams */
+  int64_t cells_live;              /* mark: cells whose hit the call raised to its stamp; compose: live cells */
+  int64_t cells_cleared;           /* mark: cells whose clear the call raised to its stamp; compose: cells that are
+                                      not live with clear > hit, within persist */
+  int64_t cells_free, cells_occupied, cells_unknown;  /* compose: cells by composed value (any other byte: free) */
+  int64_t cells_raised;            /* compose: live cells whose base is not VG_OCC_OCCUPIED */
+  int64_t stamp;                   /* mark: the stamp the call used; compose: now; totals: the largest stamp so far */
+  int64_t calls;                   /* totals: vg_live_mark calls that succeeded; else 0 */
+  int64_t reserved;
+} vg_live_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vg_live_params) == 224 && sizeof(vg_live_point) == 32 && sizeof(vg_live_summary) == 128,
+              "the live layer's records have no implicit padding");
+#else
+_Static_assert(sizeof(vg_live_params) == 224 && sizeof(vg_live_point) == 32 && sizeof(vg_live_summary) == 128,
+               "the live layer's records have no implicit padding");
+#endif
+/* vg_live_begin creates the layer. base_grid: nx ny int8 on the host, or NULL: a
+ * copy of the grid the last vg_occupancy / vg_terrain / vg_live_compose call on this
+ * context left on the device. VG_E_ARG (nothing is created): NULL ctx or prm; res
+ * not finite or <= 0; x0 or y0 not finite; nx or ny < 1 or > VG_CLR_MAX_SIDE, or nx
+ * ny > VG_OCC_MAX_CELLS; a band limit that is not finite, z_lo <= 0 <= z_hi or z_lo <
+ * z_hi not true; clear_max / res > 4096; flags with a bit above 0. VG_E_STATE: the
+ * context is sharded (world > 1), has a layer already, or base_grid is NULL and no
+ * grid is held or its nx, ny differ from prm's.
+ * vg_live_mark: xyz, n and pose12 as vg_scan_diff's (pose12 NULL: the context's
+ * current state); stamp as above; per_point (may be NULL): n records; out (may be
+ * NULL): the call's summary. The class of a record and n[] are vg_scan_diff's for
+ * the same input. The _dev form takes the cloud as three device arrays. n == 0 is
+ * legal and takes its stamp. VG_E_ARG (nothing is written, no stamp is taken):
+ * NULL ctx, NULL xyz or device array with n > 0, n < 0 or above
+ * max_points_per_scan, stamp < 0. VG_E_RANGE: stamp == 0 after the largest stamp
+ * reached INT32_MAX. VG_E_STATE: no layer, or the context is sharded.
+ * vg_live_compose: now > 0, or 0 for the layer's largest stamp so far; flags as
+ * above; grid (may be NULL: the composed grid stays on the device only): nx ny
+ * int8. VG_E_ARG: NULL ctx, now < 0, flags with a bit above 0. VG_E_STATE as above.
+ * vg_live_info copies the planes (nx ny int32 each) and the totals: the sums of the
+ * marks' summaries since the layer began or was cleared. vg_live_clear zeroes the
+ * planes and the totals and restarts the stamps; the base stays. vg_live_end frees
+ * the layer; vg_destroy and vg_reset free it too. VG_E_STATE without a layer.
+ * Legal where vg_scan_diff is: completes outstanding work first; mapping on or off;
+ * on an owner, an attached tracker and a fleet's tracker between fleet steps. The
+ * calls read the map only. A fleet shares obstacles by marking every tracker's scan,
+ * with that tracker's pose, into one context's layer; the calls into one layer come
+ * from one thread at a time. The layer is not part of a checkpoint. */
+int vg_live_begin(vg_ctx* ctx, const vg_live_params* prm, const int8_t* base_grid);
+int vg_live_mark(vg_ctx* ctx, const float* xyz, int n, const double* pose12, int32_t stamp,
+                 vg_live_point* per_point, vg_live_summary* out);
+int vg_live_mark_dev(vg_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int n,
+                     const double* pose12, int32_t stamp, vg_live_summary* out);
+int vg_live_compose(vg_ctx* ctx, int32_t now, int flags, int8_t* grid, vg_live_summary* out);
+int vg_live_info(vg_ctx* ctx, int32_t* hit, int32_t* clear, vg_live_summary* totals);
+int vg_live_clear(vg_ctx* ctx);
+int vg_live_end(vg_ctx* ctx);
+
 /* ---- Place index: global relocalisation in a frozen map ------------------------
  * vg_relocalize needs a rough guess. The place index supplies one from a single
  * scan and the gravity direction: a side structure next to a frozen map (as the

@@ -358,6 +358,36 @@ class LioCore {
   }
   void change_clear() { check(vg_change_clear(ctx_), "vg_change_clear"); }
   void change_end() { check(vg_change_end(ctx_), "vg_change_end"); }
+  // the live obstacle layer (vina_gpu.h "Live obstacle layer") of this context: base_grid null: a copy of the grid
+  // the last occupancy() call left on the device; stamp 0: the largest so far + 1; now 0: the largest stamp
+  void live_begin(const vg_live_params& prm, const int8_t* base_grid = nullptr) {
+    check(vg_live_begin(ctx_, &prm, base_grid), "vg_live_begin");
+  }
+  vg_live_summary live_mark(const float* xyz, int n, const double* pose12 = nullptr, int32_t stamp = 0,
+                            vg_live_point* per_point = nullptr) {
+    vg_live_summary out;
+    check(vg_live_mark(ctx_, xyz, n, pose12, stamp, per_point, &out), "vg_live_mark");
+    return out;
+  }
+  vg_live_summary live_mark_dev(const float* d_x, const float* d_y, const float* d_z, int n,
+                                const double* pose12 = nullptr, int32_t stamp = 0) {
+    vg_live_summary out;
+    check(vg_live_mark_dev(ctx_, d_x, d_y, d_z, n, pose12, stamp, &out), "vg_live_mark_dev");
+    return out;
+  }
+  // grid null: the composed grid stays on the device, where clearance(nullptr, ...) reads it
+  vg_live_summary live_compose(int32_t now = 0, int flags = 0, int8_t* grid = nullptr) {
+    vg_live_summary out;
+    check(vg_live_compose(ctx_, now, flags, grid, &out), "vg_live_compose");
+    return out;
+  }
+  vg_live_summary live_info(int32_t* hit = nullptr, int32_t* clear = nullptr) {
+    vg_live_summary out;
+    check(vg_live_info(ctx_, hit, clear, &out), "vg_live_info");
+    return out;
+  }
+  void live_clear() { check(vg_live_clear(ctx_), "vg_live_clear"); }
+  void live_end() { check(vg_live_end(ctx_), "vg_live_end"); }
   // the place index (vina_gpu.h "Place index"): build / end on the map's owner; info, scan, query and
   // relocalize_global on the owner or any tracker attached to it. R_level9 null: the current R
   void places_build(const double* positions, int M, const vg_places_params* prm = nullptr) {

@@ -533,6 +533,43 @@ class NodeCore {
     return c;
   }
 
+  // The live obstacle layer over g (vg_live_begin; vina_gpu.h "Live obstacle layer"): prm's band, ranges, persist,
+  // flags and diff parameters, its geometry taken from g. on_device as costmap()'s: g is the grid that lies on the
+  // device, which the layer copies there. Completes outstanding work.
+  void live_begin(const OccupancyGrid& g, vg_live_params prm = vg_live_params(), bool on_device = false) {
+    finish();
+    prm.x0 = g.x0, prm.y0 = g.y0, prm.res = g.res, prm.nx = g.nx, prm.ny = g.ny;
+    if (!on_device && g.data.size() != (size_t)g.nx * (size_t)g.ny) throw Error(VG_E_ARG, "live_begin: the grid's data is not nx ny cells");
+    lio_.live_begin(prm, on_device ? nullptr : g.data.data());
+    live_g_ = OccupancyGrid();
+    live_g_.x0 = g.x0, live_g_.y0 = g.y0, live_g_.res = g.res, live_g_.nx = g.nx, live_g_.ny = g.ny;
+  }
+  void live_end() {
+    finish();
+    lio_.live_end();
+    live_g_ = OccupancyGrid();
+  }
+  // What the planner gets of a scan: the scan (n points, LiDAR frame; pose12 null: the current state) marked into
+  // the layer (vg_live_mark, stamp 0: the next), the layer composed at that stamp (vg_live_compose) and the composed
+  // grid priced where it lies on the device (costmap(..., on_device)). plan() and frontiers() then read that costmap.
+  struct LiveCostmap {
+    OccupancyGrid grid;  // the composed grid, with the layer's geometry
+    Costmap costmap;
+    vg_live_summary mark = {}, compose = {};
+  };
+  LiveCostmap live_costmap(const float* xyz, int n, const double* pose12, double inscribed, double inflation,
+                           double scaling, int32_t stamp = 0, int compose_flags = 0, int cost_flags = 0) {
+    finish();
+    if (!live_g_.nx) throw Error(VG_E_STATE, "live_costmap: no live_begin() on this node yet");
+    LiveCostmap r;
+    r.grid = live_g_;
+    r.grid.data.resize((size_t)live_g_.nx * (size_t)live_g_.ny);
+    r.mark = lio_.live_mark(xyz, n, pose12, stamp);
+    r.compose = lio_.live_compose((int32_t)r.mark.stamp, compose_flags, r.grid.data.data());
+    r.costmap = costmap(r.grid, inscribed, inflation, scaling, cost_flags, true);
+    return r;
+  }
+
   // The path from start_xy to goal_xy (world metres) over the last costmap() of this node, whose cost plane is read
   // where vg_clearance left it on the device (no vg_clearance may have run on the context since): vg_navfn towards
   // the goal's cell with prm's traversal table (null: nav2's defaults), then vg_nav_paths from the start's cell,
@@ -806,6 +843,7 @@ class NodeCore {
   int publish_ = 0;  // vg_set_publish flags
   double cm_x0_ = 0, cm_y0_ = 0, cm_res_ = 0;  // the last costmap()'s geometry (plan())
   int cm_nx_ = 0, cm_ny_ = 0;
+  OccupancyGrid live_g_;  // the live layer's geometry (live_begin(); nx 0: none)
   bool visualization_ = false;
   std::function<void()> after_step_;
   std::vector<vg_plane_marker> markers_, marker_buf_;

@@ -527,6 +527,26 @@ struct ChangeLayer {
   DevBuf<int> blk;       // the report's per-workgroup counts / offsets
   DevBuf<char> out;      // the report's record staging (bytes), grown on demand
 };
+// The live obstacle layer (vina_gpu.h "Live obstacle layer"; live.hip, live_host.cpp): the two stamp planes beside a
+// private base grid, owned by the context it was begun on. Only integer atomic maxima write the planes.
+struct LivePrm {  // vg_live_params with the defaults applied (the diff parameters: LiveLayer::diff)
+  double x0, y0, res;
+  double z_lo, z_hi, r_min, mark_max, clear_max;
+  int nx, ny;
+  int persist, unknown_marks;
+};
+struct LiveLayer {
+  LivePrm q;
+  vg_diff_params diff;        // as vg_live_begin was given them
+  int stamp = 0;              // the largest stamp so far
+  vg_live_summary tot = {};   // the marks' summaries summed (host side)
+  DevBuf<int8_t> base;        // cells
+  DevBuf<int> hit, clear;     // cells each
+  DevBuf<vg_live_point> rec;  // the last mark's records, grown to the count a call brings
+  DevBuf<unsigned long long> sum;  // vg_live_summary's 16 slots as the kernels index them
+  DevBuf<int> cls;            // diff_wave_counts' six ints
+  KernelTimer t_mark, t_walk, t_comp;  // around the last mark's kernels, its k_live_walk, the last compose (vgx_live_ms)
+};
 // The place index (vina_gpu.h "Place index"; places.hip, places_host.cpp): a side
 // structure of the context that owns a frozen map, like the change layer. One
 // query at a time (vg_ctx::places_mu of the owner): the scan's histogram, its
@@ -689,6 +709,7 @@ struct vg_ctx {
   vg::ChangeLayer* change = nullptr;  // the change layer of this context's map (vg_change_begin .. vg_change_end)
   std::mutex change_mu;      // serialises every call into this context's layer, vg_change_end included: a caller
                              // (the owner or an attached tracker) reads `change` only while holding it
+  vg::LiveLayer* live = nullptr;     // the live obstacle layer of this context (vg_live_begin .. vg_live_end)
   vg::PlaceIndex* places = nullptr;  // the place index of this context's map (vg_places_build .. vg_places_end)
   std::mutex places_mu;      // the same discipline for `places`
   vg_stats stats;
@@ -1171,6 +1192,15 @@ int change_accum_dev(vg_ctx* ctx, ChangeLayer* L, const MP& mp, const float* x, 
 // every selected record, in report order; tot4: points dropped, out of range, nodes touched, cells used
 int change_report_dev(vg_ctx* ctx, ChangeLayer* L, const vg_change_query& q, std::vector<vg_change_leaf>& leaves,
                       std::vector<vg_change_cell>& cells, long long* tot4);
+// live.hip: the live obstacle layer's device side; synchronous on the context stream, which the caller drained.
+// Arguments: checked by the caller
+int live_alloc(vg_ctx* ctx, LiveLayer* L, const int8_t* base_grid);  // the planes zeroed, the base from the host or the held grid
+int live_clear_dev(vg_ctx* ctx, LiveLayer* L);
+// one scan into L at `stamp`; x, y, z: host AoS (stride 3, dev false) or device arrays (stride 1)
+int live_mark_dev(vg_ctx* ctx, LiveLayer* L, const MP& mp, const float* x, const float* y, const float* z, int stride,
+                  bool dev, int n, const double* pose12, int stamp, vg_live_point* per_point, vg_live_summary* out);
+int live_walk_dev(vg_ctx* ctx, LiveLayer* L, const vg_live_point* recs, int n, int stamp);  // k_live_walk on host records
+int live_compose_dev(vg_ctx* ctx, LiveLayer* L, int now, int flags, int8_t* grid, vg_live_summary* out);
 // places.hip: the place index's device side. The caller holds the owner's places_mu and has drained ctx's stream
 int places_prm_ok(const vg_places_params* prm, int* A, int* E);  // VG_E_ARG: a limit exceeded, a bad span
 int places_dirs(const vg_places_params* prm, double* out, int cap, int* count);
@@ -1210,6 +1240,14 @@ int host_frontiers(vg_ctx* ctx, const int8_t* grid, const uint8_t* cost, const v
 // view_host.cpp: the call behind the C-ABI
 int host_view_gain(vg_ctx* ctx, const int8_t* grid, const vg_view_params* prm, const int32_t* views, int n_views,
                    vg_view_rec* recs, int32_t* seen, vg_view_summary* out);
+// live_host.cpp: the calls behind the C-ABI
+int host_live_begin(vg_ctx* ctx, const vg_live_params* prm, const int8_t* base_grid);
+int host_live_mark(vg_ctx* ctx, const float* xyz, const float* d_x, const float* d_y, const float* d_z, int n,
+                   const double* pose12, int stamp, vg_live_point* per_point, vg_live_summary* out);
+int host_live_compose(vg_ctx* ctx, int now, int flags, int8_t* grid, vg_live_summary* out);
+int host_live_info(vg_ctx* ctx, int32_t* hit, int32_t* clear, vg_live_summary* totals);
+int host_live_clear(vg_ctx* ctx);
+int host_live_end(vg_ctx* ctx);
 // localize.cpp: the frozen-map switch, scoring and relocalisation behind the C-ABI
 int host_set_mapping(vg_ctx* ctx, int on);
 int host_map_attach(vg_ctx* tracker, vg_ctx* owner);

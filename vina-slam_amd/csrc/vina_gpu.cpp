@@ -313,6 +313,7 @@ int vg_destroy(vg_ctx* ctx) {
   VG_TRY(refuse_layer(ctx, "vg_destroy", false));
   VG_TRY(refuse_fleet(ctx, "vg_destroy"));
   if (ctx->places) (void)vg_places_end(ctx);  // (no tracker reads it: the owner has no views)
+  if (ctx->live) (void)vg_live_end(ctx);
   if (ctx->view_of) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     ctx->map = ctx->own_map;
@@ -378,6 +379,7 @@ int vg_reset(vg_ctx* ctx) {
   VG_TRY(refuse_attached(ctx, "vg_reset"));
   VG_TRY(refuse_owner(ctx, "vg_reset"));
   VG_TRY(refuse_layer(ctx, "vg_reset"));
+  if (ctx->live) VG_TRY(vg_live_end(ctx));
   VG_HIP(hipStreamSynchronize(ctx->stream_ds));
   VG_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->stream_iekf) VG_HIP(hipStreamSynchronize(ctx->stream_iekf));

@@ -16,6 +16,7 @@
 //        [--checkpoint-out FILE --checkpoint-at N] [--resume FILE]
 //        [--map FILE --localize [--guess "x y z yaw" | --global [--places-step S]] [--scan-diff] [--scan-info]
 //         [--changes FILE [--changes-scans FILE]]
+//         [--live [--live-persist N] [--live-scans FILE]]  (with --costmap)
 //         [--terrain TPREFIX [--sensor-height H] [--step-max S] [--terrain-rays FILE]]
 //         [--occupancy PREFIX [--occ-res R] [--occ-rays FILE]
 //          [--costmap CPREFIX [--inscribed r] [--inflation R] [--cost-scaling s]
@@ -73,6 +74,13 @@
 // --inscribed r and --inflation R radii in metres (defaults 0.3, 1.0) and --cost-scaling s per metre (default
 // 3.0; nav2's cost_scaling_factor), and its cost written as raw bytes (254 lethal, 253 inscribed, 252 .. 1 the
 // skirt, 0 free, 255 no information) to CPREFIX.pgm, flipped as PREFIX.pgm is, with the same CPREFIX.yaml.
+// --live (with --costmap; --live-persist N: the marks live N scans; --live-scans FILE: what was marked, in
+// --changes-scans' form): every localised scan's downsampled cloud is kept with its IEKF pose; after everything
+// --costmap brings, a live obstacle layer is begun over the grid --costmap priced, where it lies on the device
+// (NodeCore::live_begin: band -0.5 .. 0.5 m about the sensor, marks between 0.5 and 8 m, beams cleared to 10 m,
+// UNKNOWN points mark too), the scans are marked in order with stamps 1, 2, ..., and the last goes through
+// NodeCore::live_costmap: the composed grid is written as CPREFIX.live.grid.pgm / .yaml in --occupancy's form, its
+// cost as CPREFIX.live.pgm / .yaml in --costmap's, and one line goes to stdout: live: N scans, K cells live.
 // --plan "gx gy" (with --costmap): the navigation function over that costmap where it lies on the device
 // (NodeCore::plan: vg_navfn with cost == NULL, nav2's default traversal table) towards the cell holding the
 // world point gx gy, and the path down it from the cell holding --from "sx sy" (default: the last pose), written
@@ -106,7 +114,9 @@ int main(int argc0, char** argv0) {
   double occ_res = 0.1, cm_inscribed = 0.3, cm_inflation = 1.0, cm_scaling = 3.0, view_radius = 0.0;
   double ter_height = 0.0, ter_step = -1.0;
   int ck_at = -1, view_max_unknown = 0;
-  bool localize = false, scan_diff = false, scan_info = false, global = false;
+  bool localize = false, scan_diff = false, scan_info = false, global = false, live = false;
+  int live_persist = 0;
+  std::string live_scans_file;
   double places_step = 1.0;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
@@ -136,6 +146,9 @@ int main(int argc0, char** argv0) {
     else if (i + 1 < argc0 && a == "--inscribed") cm_inscribed = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--inflation") cm_inflation = atof(argv0[++i]);
     else if (i + 1 < argc0 && a == "--cost-scaling") cm_scaling = atof(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--live-persist") live_persist = atoi(argv0[++i]);
+    else if (i + 1 < argc0 && a == "--live-scans") live_scans_file = argv0[++i];
+    else if (a == "--live") live = true;
     else if (a == "--localize") localize = true;
     else if (a == "--global") global = true;
     else if (a == "--scan-diff") scan_diff = true;
@@ -179,6 +192,10 @@ int main(int argc0, char** argv0) {
   }
   if (global && (!localize || !guess_s.empty() || !(places_step > 0.0))) {
     fprintf(stderr, "%s: --global needs --map FILE --localize, a positive --places-step, and no --guess\n", argv0[0]);
+    return 2;
+  }
+  if (live ? (cm_prefix.empty() || live_persist < 0) : (live_persist != 0 || !live_scans_file.empty())) {
+    fprintf(stderr, "%s: --live needs --costmap CPREFIX; --live-persist N >= 0 and --live-scans FILE go with --live\n", argv0[0]);
     return 2;
   }
   if (!changes_scans.empty() && !changes) {
@@ -318,7 +335,12 @@ int main(int argc0, char** argv0) {
         return 1;
       }
     }
-    if (scan_diff || scan_info || changes)
+    struct LiveScan {
+      std::vector<float> xyz;
+      double pose[12];
+    };
+    std::vector<LiveScan> live_scans;  // --live: every localised scan, marked at the end of the run
+    if (scan_diff || scan_info || changes || live)
       node.set_after_step([&]() {
         vg_ctx* c = node.lio().raw();
         int n = 0;
@@ -329,6 +351,12 @@ int main(int argc0, char** argv0) {
         if (n > 0 && vg_scan_points(c, ds.data(), n, &n) != VG_OK)
           throw vina_gpu::Error(VG_E_STATE, std::string("vg_scan_points: ") + vg_last_error(c));
         const double* pose = st + 1;  // R row-major, p: the pose after the scan's IEKF
+        if (live) {
+          LiveScan ls;
+          ls.xyz.assign(ds.begin(), ds.begin() + (size_t)3 * n);
+          memcpy(ls.pose, pose, sizeof(ls.pose));
+          live_scans.push_back(std::move(ls));
+        }
         if (scan_info) {
           const vg_info_rec r = node.lio().scan_info(ds.data(), n, pose);
           printf("scan_info %d %.9f %d %.9g %.9g %.9g %.9g %.9g\n", n_diffed, st[0], r.n_hits, r.eig_t[0], r.dir_t[0],
@@ -585,6 +613,41 @@ int main(int argc0, char** argv0) {
                  radius, in_view);
         }
       }
+    }
+    if (live) {
+      vg_live_params lp = {};
+      lp.z_lo = -0.5, lp.z_hi = 0.5, lp.r_min = 0.5, lp.mark_max = 8.0, lp.clear_max = 10.0;
+      lp.persist = live_persist, lp.flags = 1;
+      node.live_begin(nav, lp, true);
+      vina_gpu::NodeCore::LiveCostmap lc;
+      FILE* fl = live_scans_file.empty() ? nullptr : fopen(live_scans_file.c_str(), "wb");
+      if (!live_scans_file.empty() && !fl) {
+        perror("live-scans");
+        return 1;
+      }
+      for (size_t k = 0; k < live_scans.size(); k++) {
+        const LiveScan& ls = live_scans[k];
+        const int32_t n32 = (int32_t)(ls.xyz.size() / 3);
+        if (fl && (fwrite(&n32, sizeof(n32), 1, fl) != 1 || fwrite(ls.pose, sizeof(double), 12, fl) != 12 ||
+                   fwrite(ls.xyz.data(), sizeof(float), ls.xyz.size(), fl) != ls.xyz.size())) {
+          perror("live-scans");
+          return 1;
+        }
+        if (k + 1 < live_scans.size()) node.lio().live_mark(ls.xyz.data(), n32, ls.pose);
+        else lc = node.live_costmap(ls.xyz.data(), n32, ls.pose, cm_inscribed, cm_inflation, cm_scaling);
+      }
+      if (fl && fclose(fl) != 0) {
+        perror("live-scans");
+        return 1;
+      }
+      if (live_scans.empty()) lc = node.live_costmap(nullptr, 0, nullptr, cm_inscribed, cm_inflation, cm_scaling);
+      node.live_end();
+      if (!vina_gpu::write_occupancy_map(cm_prefix + ".live.grid", lc.grid) || !vina_gpu::write_costmap(cm_prefix + ".live", lc.costmap)) {
+        perror("live");
+        return 1;
+      }
+      printf("live: %d scans, %lld cells live, %lld raised over the grid\n", (int)live_scans.size(),
+             (long long)lc.compose.cells_live, (long long)lc.compose.cells_raised);
     }
     const std::vector<float> w = node.scan_world();
     if (!node.write_tum(argv[2])) {

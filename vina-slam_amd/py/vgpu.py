@@ -480,6 +480,46 @@ class ChangeTotals(ctypes.Structure):
                 ("leaves_touched", ctypes.c_int64), ("reserved", ctypes.c_int64 * 6)]
 
 
+class LiveParams(ctypes.Structure):
+    """vg_live_params, 224 bytes."""
+    _fields_ = [("diff", DiffParams), ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("res", ctypes.c_double),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("z_lo", ctypes.c_double), ("z_hi", ctypes.c_double),
+                ("r_min", ctypes.c_double), ("mark_max", ctypes.c_double), ("clear_max", ctypes.c_double),
+                ("persist", ctypes.c_int), ("flags", ctypes.c_int), ("reserved", ctypes.c_double * 4)]
+
+
+class LiveSummary(ctypes.Structure):
+    """vg_live_summary, 128 bytes."""
+    _fields_ = [("n", ctypes.c_int64 * 4), ("n_obstacle", ctypes.c_int64), ("marks_dropped", ctypes.c_int64),
+                ("n_beams", ctypes.c_int64), ("cells_live", ctypes.c_int64), ("cells_cleared", ctypes.c_int64),
+                ("cells_free", ctypes.c_int64), ("cells_occupied", ctypes.c_int64), ("cells_unknown", ctypes.c_int64),
+                ("cells_raised", ctypes.c_int64), ("stamp", ctypes.c_int64), ("calls", ctypes.c_int64),
+                ("reserved", ctypes.c_int64)]
+
+
+# vg_live_point (32 bytes) as a numpy record type, and its flags
+LIVE_POINT_DTYPE = np.dtype([("cls", "<i4"), ("flags", "<i4"), ("ax", "<i4"), ("ay", "<i4"), ("bx", "<i4"),
+                             ("by", "<i4"), ("mx", "<i4"), ("my", "<i4")])
+LIVE_MARKS, LIVE_CLEARS, LIVE_IN_BAND, LIVE_CUT, LIVE_LEFT_BAND = 1, 2, 4, 8, 16
+
+
+def live_params(x0=0.0, y0=0.0, res=0.0, nx=0, ny=0, z_lo=0.0, z_hi=0.0, r_min=0.0, mark_max=0.0, clear_max=0.0,
+                persist=0, flags=0, **diff):
+    """vg_live_params; zeros take the defaults (band -1 .. 1 m about the sensor, no range limits on marks, beams
+    cleared to 4096 cells or mark_max, marks kept for ever); diff: diff_params."""
+    p = LiveParams()
+    p.diff = diff_params(**diff)
+    p.x0, p.y0, p.res, p.nx, p.ny = x0, y0, res, nx, ny
+    p.z_lo, p.z_hi, p.r_min, p.mark_max, p.clear_max = z_lo, z_hi, r_min, mark_max, clear_max
+    p.persist, p.flags = persist, flags
+    return p
+
+
+def _live_summary(s):
+    return {k: (list(getattr(s, k)) if k == "n" else int(getattr(s, k))) for k, _ in LiveSummary._fields_
+            if k != "reserved"}
+
+
 class PlacesParams(ctypes.Structure):
     """vg_places_params, 144 bytes."""
     _fields_ = [("n_az", ctypes.c_int), ("n_el", ctypes.c_int), ("el_min", ctypes.c_double),
@@ -752,6 +792,18 @@ def lib():
             L.vg_view_gain.argtypes = [P, P, ctypes.POINTER(ViewParams), P, ctypes.c_int, P, P, ctypes.POINTER(ViewSummary)]
             L.vgx_view_ms.argtypes = [P, dp]
             L.vgx_view_stage.argtypes = [P, ctypes.c_int]
+        L.has_live = hasattr(L, "vg_live_begin")  # a build older than the live obstacle layer (A/B runs)
+        if L.has_live:
+            ls = ctypes.POINTER(LiveSummary)
+            L.vg_live_begin.argtypes = [P, ctypes.POINTER(LiveParams), P]
+            L.vg_live_mark.argtypes = [P, fp, ctypes.c_int, dp, ctypes.c_int32, P, ls]
+            L.vg_live_mark_dev.argtypes = [P, P, P, P, ctypes.c_int, dp, ctypes.c_int32, ls]
+            L.vg_live_compose.argtypes = [P, ctypes.c_int32, ctypes.c_int, P, ls]
+            L.vg_live_info.argtypes = [P, P, P, ls]
+            L.vg_live_clear.argtypes = [P]
+            L.vg_live_end.argtypes = [P]
+            L.vgx_live_walk.argtypes = [P, P, ctypes.c_int, ctypes.c_int32]
+            L.vgx_live_ms.argtypes = [P, dp]
         L.has_change = hasattr(L, "vg_change_begin")  # a build older than the change layer (A/B runs)
         if L.has_change:
             L.vg_change_begin.argtypes = [P, ctypes.POINTER(ChangeParams)]
@@ -892,6 +944,7 @@ class Context:
             raise VgError("vg_create failed (%d)" % r)
         self._fn_step = lib().vg_step_dev
         self._cfg = cconfig
+        self._live_shape = (1, 1)  # [ny, nx] of the live layer (live_begin); without one the library reports the state
 
     def _chk(self, r, what):
         if r != 0:
@@ -1459,6 +1512,79 @@ class Context:
     def change_end(self):
         """vg_change_end: the layer freed."""
         self._chk(lib().vg_change_end(self.h), "vg_change_end")
+
+    # ---- the live obstacle layer (vina_gpu.h "Live obstacle layer")
+    def live_begin(self, base=None, **params):
+        """vg_live_begin: params: live_params (the geometry x0, y0, res, nx, ny at least); base: int8 [ny, nx] of
+        OCC_*, or None: a copy of the grid the last occupancy() / terrain() / live_compose() left on the device."""
+        if not lib().has_live:
+            raise VgError("this libvina_gpu.so has no live obstacle layer (vg_live_begin): rebuild it")
+        p = live_params(**params)
+        b = None
+        if base is not None:
+            b = np.ascontiguousarray(base, dtype=np.int8)
+            if b.shape != (p.ny, p.nx):
+                raise ValueError("live_begin: base is [ny, nx]")
+        self._chk(lib().vg_live_begin(self.h, ctypes.byref(p), None if b is None else b.ctypes.data), "vg_live_begin")
+        self._live_shape = (p.ny, p.nx)
+
+    def live_mark(self, xyz, pose=None, stamp=0, per_point=False):
+        """vg_live_mark: the scan xyz (n, 3; LiDAR frame) at pose (12,) (None: the context's state) marked and
+        cleared into the layer at `stamp` (0: the largest so far + 1). Returns the summary as a dict; with per_point
+        also the n LIVE_POINT_DTYPE records."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pp = np.zeros(max(xyz.shape[0], 1), dtype=LIVE_POINT_DTYPE) if per_point else None
+        s = LiveSummary()
+        self._chk(lib().vg_live_mark(self.h, _f(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                     None if g is None else _d(g), stamp, None if pp is None else pp.ctypes.data,
+                                     ctypes.byref(s)), "vg_live_mark")
+        rec = _live_summary(s)
+        return (rec, pp[: xyz.shape[0]]) if per_point else rec
+
+    def live_mark_dev(self, dx, dy, dz, n, pose=None, stamp=0):
+        """vg_live_mark_dev: the cloud as three device arrays (addresses) of n floats."""
+        g = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        s = LiveSummary()
+        self._chk(lib().vg_live_mark_dev(self.h, ctypes.c_void_p(dx), ctypes.c_void_p(dy), ctypes.c_void_p(dz), n,
+                                         None if g is None else _d(g), stamp, ctypes.byref(s)), "vg_live_mark_dev")
+        return _live_summary(s)
+
+    def live_compose(self, now=0, flags=0, want_grid=True):
+        """vg_live_compose at `now` (0: the layer's largest stamp): (the composed grid int8 [ny, nx], or None with
+        want_grid False: it stays on the device for clearance(grid=None); the summary as a dict). flags bit 0: a
+        base-unknown cell a beam crossed becomes free."""
+        grid = np.zeros(self._live_shape, dtype=np.int8) if want_grid else None
+        s = LiveSummary()
+        self._chk(lib().vg_live_compose(self.h, now, flags, None if grid is None else grid.ctypes.data,
+                                        ctypes.byref(s)), "vg_live_compose")
+        return grid, _live_summary(s)
+
+    def live_info(self):
+        """vg_live_info: (hit int32 [ny, nx], clear int32 [ny, nx], the totals as a dict)."""
+        hit, clear = np.zeros(self._live_shape, dtype=np.int32), np.zeros(self._live_shape, dtype=np.int32)
+        s = LiveSummary()
+        self._chk(lib().vg_live_info(self.h, hit.ctypes.data, clear.ctypes.data, ctypes.byref(s)), "vg_live_info")
+        return hit, clear, _live_summary(s)
+
+    def live_clear(self):
+        """vg_live_clear: the planes and the totals zeroed, the stamps restart; the base stays."""
+        self._chk(lib().vg_live_clear(self.h), "vg_live_clear")
+
+    def live_end(self):
+        """vg_live_end: the layer freed."""
+        self._chk(lib().vg_live_end(self.h), "vg_live_end")
+
+    def live_walk(self, recs, stamp):
+        """vgx_live_walk (test hook): k_live_walk alone on LIVE_POINT_DTYPE records at `stamp`, into the layer."""
+        r = np.ascontiguousarray(recs, dtype=LIVE_POINT_DTYPE)
+        self._chk(lib().vgx_live_walk(self.h, r.ctypes.data if r.shape[0] else None, r.shape[0], stamp), "vgx_live_walk")
+
+    def live_ms(self):
+        """Device time (ms) of the last live_mark()'s kernels, of its k_live_walk, and of the last live_compose()."""
+        ms = (ctypes.c_double * 3)()
+        self._chk(lib().vgx_live_ms(self.h, ms), "vgx_live_ms")
+        return tuple(ms)
 
     # ---- the place index (vina_gpu.h "Place index")
     def places_build(self, positions, **params):
